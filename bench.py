@@ -7,13 +7,15 @@ weights) are already resident in HBM.  Frame-pairs are independent, so with N GP
 its own batch (weak scaling, no data-path collective); the only collectives are the barrier and the MAX over ranks of
 the elapsed time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no launcher environment starts its own N ranks (fresh child processes, one per
 GPU, started before this process touches the GPU; rank 0's JSON line is the output).  Rank 0 prints ONE JSON line (see
-DESIGN.md "Measurement" for the definition of every field).  On one GPU the same line carries, under `extra`, the other
-operating points SURVEY.md 8(d) asks for, measured by the same process right after the headline run: frame-pairs per step
+DESIGN.md "Measurement" for the definition of every field).  A plain run sets up, warms up, times K steps, writes the last
+step's outputs under --dump-outputs DIR if given, and prints the line.  With --full the same process also reads the energy
+counter and self-checks the headline batch, times the CPU baseline, and, on one GPU, measures under `extra` (in the long
+form, --extra-file) the other operating points SURVEY.md 8(d) asks for, right after the headline run: frame-pairs per step
 1 / 8 / 64 / 512 (the reference's eval loop runs batch 1; 512 was the headline batch of rounds 1 - 2), the strict-f32, bf16-piece and
 opt-in fixed-grid arithmetic at 512 per step, and the reference's shipped car configuration (max_obj 90, num_point 5 -> F = 320,
 num_feats 3).
@@ -210,9 +212,10 @@ class Bench:
             self.dist.barrier()
         self.torch.cuda.synchronize()
 
-    def measure(self, cfg, B, steps, warmup, arithmetic, graph=False, energy=None, selfcheck=False):
+    def measure(self, cfg, B, steps, warmup, arithmetic, graph=False, energy=None, selfcheck=False, keep_outputs=False):
         """W untimed + K timed steps of B frame-pairs (the first B of the resident inputs) bracketed by barrier + synchronize; HIP
-        events around the two heaviest kernels of every timed step, on the launch stream (shasta_affinity_forward_timed_f32)."""
+        events around the two heaviest kernels of every timed step, on the launch stream (shasta_affinity_forward_timed_f32).
+        keep_outputs: the result also holds `outputs` = (matched1, matched2) of the last timed step."""
         torch, hip, lib = self.torch, self.hip, self.lib
         model = self.model(cfg)
         model.arithmetic = arithmetic
@@ -296,9 +299,12 @@ class Bench:
             pair.append(ms.value)
             for e in four:
                 lib.shasta_event_destroy(e)
-        return dict(B=B, steps=steps, warmup=warmup, elapsed=elapsed, ms_per_step=elapsed / steps * 1e3,
-                    value=self.world * B * steps / elapsed, l1_ms=sum(l1) / len(l1), pair_ms=sum(pair) / len(pair), joules=joules,
-                    selfcheck=check)
+        r = dict(B=B, steps=steps, warmup=warmup, elapsed=elapsed, ms_per_step=elapsed / steps * 1e3,
+                 value=self.world * B * steps / elapsed, l1_ms=sum(l1) / len(l1), pair_ms=sum(pair) / len(pair), joules=joules,
+                 selfcheck=check)
+        if keep_outputs:
+            r["outputs"] = (m1, m2)
+        return r
 
 
 def rooflines(cfg, arithmetic, r, with_traffic=True):
@@ -431,6 +437,13 @@ def main():
                     help="where the long form goes (full roofline objects, the other operating points of SURVEY 8(d), notes); also printed to stderr")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous / reduction plumbing only, on the CPU with gloo (no GPU, no forward): for the CPU test suite")
+    ap.add_argument("--full", action="store_true",
+                    help="measure more than the headline: the energy counter around the timed steps, the self-check of the headline batch, the "
+                         "other operating points (`extra`, unless --no-extras), the CPU baseline (unless --no-cpu-baseline) and the long form "
+                         "in --extra-file.  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write matched1 / matched2 of the last one as DIR/matched1.npy and DIR/matched2.npy "
+                         "(float32, at most %d MB together: a fixed sample of the batch's frame-pairs, see dump_outputs)" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -457,8 +470,13 @@ def main():
     PRECUT = not args.no_precut
     bench = Bench(args, dev, rank, world, dist)
     B = args.batch
-    energy = EnergyCounter(dev)
-    r = bench.measure(HEADLINE, B, args.steps, args.warmup, args.arithmetic, graph=args.graph, energy=energy, selfcheck=True)
+    # a plain run times the headline and nothing else; the energy counter and the self-check come with --full
+    energy = EnergyCounter(dev) if args.full else None
+    dump = bool(args.dump_outputs) and rank == 0
+    r = bench.measure(HEADLINE, B, args.steps, args.warmup, args.arithmetic, graph=args.graph, energy=energy, selfcheck=args.full,
+                      keep_outputs=dump)
+    if dump:
+        dump_outputs(args.dump_outputs, *r.pop("outputs"))
     roof_l1, roof_pair = rooflines(HEADLINE, args.arithmetic, r)
     # `roofline` is the kernel with the longer average launch; the other one rides along as `roofline_second`
     roof, second = (roof_l1, roof_pair) if r["l1_ms"] >= r["pair_ms"] else (roof_pair, roof_l1)
@@ -468,31 +486,33 @@ def main():
     if probe:
         out["probe"] = True
         out["probe_value"] = r["value"]
-    # everything else (the full roofline objects, the other operating points, notes) goes to a side file and to stderr: the last stdout
-    # line stays a few hundred bytes per object (round 5's 22 KB line was not parsed by the driver)
-    detail = {"headline": {"value": r["value"], "ms_per_step": r["ms_per_step"], "frame_pairs_per_step": B,
-                           "dense_equivalent_tflops": DENSE_GFLOP_PER_PAIR * 1e9 * r["value"] / 1e12,
-                           "hip_graph": bool(args.graph), "precut_weight_stream": not args.no_precut,
-                           "arithmetic_note": ARITHMETIC_NOTES[args.arithmetic],
-                           "energy": None if joules is None else {"joules_per_step": joules / args.steps, "avg_power_w": joules / elapsed,
-                                                                  "millijoules_per_frame_pair": joules / args.steps / B * 1e3, "pci": energy.pci},
-                           "roofline": roof, "roofline_second": second}}
-    if rank == 0 and world == 1 and not args.no_extras and not args.graph:
-        try:
-            detail["extra"] = extras(bench, args)
-            f32 = detail["extra"].get("arithmetic_f32", {})
-            out["value_f32"] = f32.get("value")
-        except Exception as err:  # noqa: BLE001  (the headline above is measured: never lose the line to an extra)
-            detail["extra"] = {"error": "%s: %s" % (type(err).__name__, str(err)[:300])}
+    if args.full:
+        # everything else (the full roofline objects, the other operating points, notes) goes to a side file and to stderr: the last stdout
+        # line stays a few hundred bytes per object (round 5's 22 KB line was not parsed by the driver)
+        detail = {"headline": {"value": r["value"], "ms_per_step": r["ms_per_step"], "frame_pairs_per_step": B,
+                               "dense_equivalent_tflops": DENSE_GFLOP_PER_PAIR * 1e9 * r["value"] / 1e12,
+                               "hip_graph": bool(args.graph), "precut_weight_stream": not args.no_precut,
+                               "arithmetic_note": ARITHMETIC_NOTES[args.arithmetic],
+                               "energy": None if joules is None else {"joules_per_step": joules / args.steps, "avg_power_w": joules / elapsed,
+                                                                      "millijoules_per_frame_pair": joules / args.steps / B * 1e3, "pci": energy.pci},
+                               "roofline": roof, "roofline_second": second}}
+        if rank == 0 and world == 1 and not args.no_extras and not args.graph:
+            try:
+                detail["extra"] = extras(bench, args)
+                f32 = detail["extra"].get("arithmetic_f32", {})
+                out["value_f32"] = f32.get("value")
+            except Exception as err:  # noqa: BLE001  (the headline above is measured: never lose the line to an extra)
+                detail["extra"] = {"error": "%s: %s" % (type(err).__name__, str(err)[:300])}
     if args.arithmetic == "f32":
         out["value_f32"] = out["value"]
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(bench.model(HEADLINE), args.cpu_sample)
         except Exception as err:  # noqa: BLE001
             out["cpu_baseline"] = {"error": "%s: %s" % (type(err).__name__, str(err)[:200]), "kind": "port"}
     if rank == 0:
-        out["extra_file"] = write_extra(detail, args.extra_file)
+        if args.full:
+            out["extra_file"] = write_extra(detail, args.extra_file)
         emit(out)
     if world > 1:
         dist.destroy_process_group()
@@ -545,6 +565,24 @@ def compact_roofline(ro):
     c = {k: ro[k] for k in keep if k in ro}
     c["kernel"] = ro["kernel"].split(":")[0].split(" (")[0]
     return c
+
+
+DUMP_BYTES = 32 << 20  # --dump-outputs: at most this much in all (16 frame-pairs at the headline size, 2 MB of matched1 + matched2 each)
+
+
+def dump_outputs(path, m1, m2):
+    """--dump-outputs: what a caller of Shasta.affinity_from_bev received from the last timed step, matched1 (B, N, N + 2) and
+    matched2 (B, N + 2, N), as float32 `path`/matched1.npy and matched2.npy.  The whole batch when it fits in DUMP_BYTES; otherwise the
+    frame-pairs numpy.random.default_rng(0) picks, in ascending order - the same ones in every run with the same --batch."""
+    import numpy as np
+    import torch
+    B = m1.shape[0]
+    k = max(1, min(B, DUMP_BYTES // ((m1[0].numel() + m2[0].numel()) * 4)))
+    idx = np.arange(B) if k == B else np.sort(np.random.default_rng(0).choice(B, size=k, replace=False))
+    sel = torch.as_tensor(idx, device=m1.device)
+    os.makedirs(path, exist_ok=True)
+    for name, t in (("matched1", m1), ("matched2", m2)):
+        np.save(os.path.join(path, name + ".npy"), t.index_select(0, sel).float().cpu().numpy())
 
 
 def write_extra(detail, path):

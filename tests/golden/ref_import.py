@@ -1,7 +1,7 @@
 """Import helpers for the upstream reference at /root/reference (build container ONLY).
 
 Nothing here runs on the GPU box: /root/reference does not exist there.  This module is
-used by make_golden.py (fixture generation) and by the optional `-m ref` cross-checks.
+used by the make_*_golden.py scripts (fixture generation).
 It never copies reference source; it imports it in place with the absent third-party
 packages stubbed.
 """

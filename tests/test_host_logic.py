@@ -1,7 +1,6 @@
 """CPU tests of the host-side mirror: decode loop, association surface, scene sharding + 2-process gloo gather."""
 import copy
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -99,22 +98,23 @@ def test_association_affinity_and_euler_modes():
             A.associate_dets_to_tracks(dets, trks, "greedy", "iou")
 
 
-@pytest.mark.ref
 def test_association_matches_reference_module():
-    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
-    import ref_import as R
-    ref = R.import_association()
-    from mot_3d.data_protos import BBox
-    rng = np.random.default_rng(2)
-    for mode in ("greedy", "bipartite"):
-        for asso in ("euler", "m_dis"):
-            dets = [BBox.array2bbox(rng.normal(size=7) * [5, 5, 1, 3, 1, 1, 1]) for _ in range(7)]
-            trks = [BBox.array2bbox(rng.normal(size=7) * [5, 5, 1, 3, 1, 1, 1]) for _ in range(5)]
-            inn = [np.eye(7) * rng.uniform(0.5, 2) + 0.1 for _ in trks] if asso == "m_dis" else None
-            r = ref.associate_dets_to_tracks(dets, trks, mode, asso, 3.0, inn)
-            g = A.associate_dets_to_tracks(dets, trks, mode, asso, 3.0, inn)
-            assert [tuple(int(v) for v in x) for x in r[0]] == [tuple(int(v) for v in x) for x in g[0]]
-            assert [int(v) for v in r[1]] == [int(v) for v in g[1]] and [int(v) for v in r[2]] == [int(v) for v in g[2]]
+    """Against the reference's mot_3d.association on seeded boxes (tests/golden/association_golden.json, made by
+    tests/golden/make_association_golden.py): the same matches and unmatched lists, in the same order."""
+    import json
+    from types import SimpleNamespace
+    with open(os.path.join(os.path.dirname(__file__), "golden", "association_golden.json")) as f:
+        cases = json.load(f)["cases"]
+    assert len(cases) == 4
+
+    def bbox(a):  # the attributes mot_3d's BBox.array2bbox sets
+        return SimpleNamespace(**dict(zip(("x", "y", "z", "o", "l", "w", "h"), a)))
+    for c in cases:
+        dets, trks = [bbox(d) for d in c["dets"]], [bbox(t) for t in c["trks"]]
+        inn = None if c["innovation"] is None else [np.array(m, np.float64) for m in c["innovation"]]
+        g = A.associate_dets_to_tracks(dets, trks, c["mode"], c["asso"], c["dist_threshold"], inn)
+        assert [tuple(x) for x in c["matches"]] == [tuple(int(v) for v in x) for x in g[0]], (c["mode"], c["asso"])
+        assert c["unmatched_dets"] == [int(v) for v in g[1]] and c["unmatched_trks"] == [int(v) for v in g[2]], (c["mode"], c["asso"])
 
 
 def test_shard_scenes_is_a_balanced_partition():

@@ -6,7 +6,7 @@ mkdir -p $O
 cd $R
 python -m pytest tests -m gpu -q --tb=short -rf -x > $O/pytest.log 2>&1
 grep -n "passed\|failed" $O/pytest.log | tail -3
-python bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err
+python bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err
 tail -2 $O/bench.err
 python - <<PY
 import json

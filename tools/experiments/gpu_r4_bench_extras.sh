@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/${1:-r4g}
 mkdir -p $O
 cd $R
-T0=$(date +%s.%N); python bench.py > $O/bench.json 2> $O/bench.err; T1=$(date +%s.%N); echo "bench wall $(echo "$T1 - $T0" | bc) s"
+T0=$(date +%s.%N); python bench.py --full > $O/bench.json 2> $O/bench.err; T1=$(date +%s.%N); echo "bench wall $(echo "$T1 - $T0" | bc) s"
 tail -3 $O/bench.err
 python - <<PY
 import json

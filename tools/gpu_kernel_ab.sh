@@ -13,7 +13,7 @@ for rep in 1 2; do
 for lib in "" "$@"; do
   n=default; [ -n "$lib" ] && n=$(basename $lib .so)
   rm -rf $O/ab_$n
-  SHASTA_HIP_LIB=${lib:+$R/$lib} rocprofv3 --kernel-trace --output-format csv -d $O/ab_$n -o p -- python3 $R/bench.py --batch 1024 --steps 10 --warmup 3 --no-cpu-baseline --no-extras > $O/ab_$n.log 2>&1
+  SHASTA_HIP_LIB=${lib:+$R/$lib} rocprofv3 --kernel-trace --output-format csv -d $O/ab_$n -o p -- python3 $R/bench.py --batch 1024 --steps 10 --warmup 3 --full --no-cpu-baseline --no-extras > $O/ab_$n.log 2>&1
   python3 - <<PY
 import csv,glob,json
 for f in glob.glob("$O/ab_$n/**/*kernel_trace.csv", recursive=True):

@@ -8,7 +8,7 @@ for m in pieces f32 f16x2; do
   cat $O/check_$m.json
 done
 for m in pieces f16x2; do
-  python bench.py --no-cpu-baseline --steps 30 --arithmetic $m > $O/bench_$m.json 2> $O/bench_$m.err
+  python bench.py --full --no-cpu-baseline --steps 30 --arithmetic $m > $O/bench_$m.json 2> $O/bench_$m.err
   python - <<PY
 import json
 d=json.loads(open("$O/bench_$m.json").read().strip().splitlines()[-1])

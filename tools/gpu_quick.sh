@@ -7,7 +7,7 @@ mkdir -p $O
 cd $R
 python -m pytest tests/test_hip_parity.py tests/test_fuzz.py -m gpu -q -x --tb=short -k "${2:-forward or headline or batched or edge or operating or f32_arith or fuzz or large}" > $O/pytest.log 2>&1
 tail -4 $O/pytest.log
-python bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err
+python bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err
 python - <<PY
 import json
 d=json.loads(open("$O/bench.json").read().strip().splitlines()[-1])

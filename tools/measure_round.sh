@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/${1:-final}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py --extra-file $O/bench_extra.json > $O/bench_default.json 2> $O/bench_default.err   # the driver's line (compact) + the long form: extra.{batch_sweep, arithmetic_*, car_90_320_3, ...}
+python3 $R/bench.py --full --extra-file $O/bench_extra.json > $O/bench_default.json 2> $O/bench_default.err   # the driver's line (compact) + the long form: extra.{batch_sweep, arithmetic_*, car_90_320_3, ...}
 for b in 1 64 128 512; do
   python3 $R/bench.py --batch $b --no-cpu-baseline --no-extras > $O/bench_b$b.json 2> /dev/null
 done
