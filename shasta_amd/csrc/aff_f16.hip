@@ -250,7 +250,6 @@ __device__ __forceinline__ void aq_mlp(const AffPiecesArgs& a, char* smem, int g
     const float* sec = reinterpret_cast<const float*>(a.wp);
     const f32x16 zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const int n = lane & 31, hh = lane >> 5, rbw = wid >> 1;
-    AP_STAMP(0);
 
     // ---- layer 1 (K = D -> 128): wave = (row block wid >> 1, feature blocks 2 (wid & 1) + {0, 1}) ----
     f32x16 out0 = zero16, out1 = zero16;
@@ -381,7 +380,6 @@ __device__ __forceinline__ void aq_mlp(const AffPiecesArgs& a, char* smem, int g
             slot = nslot;
         }
     }
-    AP_STAMP(1);
     const qu32x4* w2 = wq + ap16_frag_offset(1, D) * 64;
     const qu32x4* w3 = wq + ap16_frag_offset(2, D) * 64;
     const qu32x4* w4 = wq + ap16_frag_offset(3, D) * 64;
@@ -432,7 +430,6 @@ __device__ __forceinline__ void aq_mlp(const AffPiecesArgs& a, char* smem, int g
         aq_activate(h[1], fb0 + 1, hh, r5, sec + ap16_scale_offset(4, D), a.bias[4]);
         aq_finish<2, AP_AROW, AIMG>(h, fbs, rbw, true, true, HA, pm, rsc0, lane, wid);
     }
-    AP_STAMP(2);
     // ---- layer 6 (128 -> D): wave = feature blocks {wid + WAVES i} x the RB row blocks; every weight fragment feeds RB x 3 MFMAs, the
     // fragments of the next k step are requested before the MFMAs of this one ----
     const int nfb = ap_fblocks(5, D);
@@ -474,7 +471,6 @@ __device__ __forceinline__ void aq_mlp(const AffPiecesArgs& a, char* smem, int g
     }
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) rs[rb] = rsc0[rb * 32 + n];
-    AP_STAMP(3);
 }
 
 template <int ROWS, int WAVES>
@@ -538,13 +534,7 @@ int launch_aff_frame16(const shasta_weights* w, const float* packed16, const flo
     a.ld = ld;
     a.ldm = ldm;
     fa.m2 = m2;
-#if defined(AP_SHAPE_64)
-    return launch_aff_frame16_shape<64, 4>(fa, B, ws, st);
-#elif defined(AP_SHAPE_128)
-    return launch_aff_frame16_shape<128, 8>(fa, B, ws, st);
-#else
     return B * cdiv(T, 128) >= 256 ? launch_aff_frame16_shape<128, 8>(fa, B, ws, st) : launch_aff_frame16_shape<64, 4>(fa, B, ws, st);
-#endif
 }
 
 }  // namespace shasta

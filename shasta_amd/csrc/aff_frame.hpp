@@ -34,14 +34,6 @@ struct ApShape {
     static_assert(PER * (NS - 1) <= 63, "vmcnt is 6 bits");
 };
 
-#ifdef SHASTA_AFF_STAMP  // diagnostic build only (tools/probes/aff_probe.hip): s_memtime at the phase boundaries of a workgroup
-__device__ unsigned long long g_aff_stamp[4096][8];
-#define AP_STAMP(i) \
-    if (threadIdx.x == 0 && blockIdx.x < 4096) g_aff_stamp[blockIdx.x][i] = __builtin_amdgcn_s_memtime()
-#else
-#define AP_STAMP(i)
-#endif
-
 struct AffPiecesArgs {
     const uint32_t* wp;  // piece fragments of the six layers
     const float* bias[6];
@@ -88,9 +80,6 @@ __host__ __device__ inline size_t aff_frame_ctrl_bytes(int B) { return ((size_t)
 // `slot`: four bytes of LDS nobody else touches until the second barrier.
 __device__ __forceinline__ unsigned ap_take_ticket(const AffFrameArgs& fa, unsigned* slot) {
     if (fa.G <= 1) return blockIdx.x;
-#ifdef SHASTA_AFF_NO_TICKET  // A/B diagnostic only (tools/gpu_aff_ab.sh): block ids as tiles, i.e. trust in-order dispatch
-    return blockIdx.x;
-#endif
     if (threadIdx.x == 0) *slot = __hip_atomic_fetch_add(fa.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
     const unsigned t = *slot;
@@ -277,7 +266,6 @@ __device__ __forceinline__ void ap_frame_tail(const AffFrameArgs& fa, char* smem
             __hip_atomic_store(mypart + 512 + c, csuml[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
-    AP_STAMP(4);
     bool poisoned = false;
     // Write-out in two passes of HR = ROWS / 2 rows through the staging [HR][512 + 4]: a wave then owns WHOLE rows - its stores of one
     // row are 2 KB contiguous and the eight waves write eight consecutive rows, i.e. the workgroup walks linearly through its (dense)
@@ -317,9 +305,7 @@ __device__ __forceinline__ void ap_frame_tail(const AffFrameArgs& fa, char* smem
                     const unsigned mine = 1u;
 #endif
                     // release: the partials of this workgroup (complete, see above) are ordered before the count the siblings poll
-#ifndef SHASTA_AFF_NO_FENCE  // (A/B diagnostic only, tools/gpu_aff_ab.sh)
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-#endif
                     // polled with the same read-modify-write path that counts the arrivals
                     unsigned seen = __hip_atomic_fetch_add(fa.arrive + b, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + mine, spins = 0;
                     while (seen < (unsigned)G) {
@@ -331,9 +317,7 @@ __device__ __forceinline__ void ap_frame_tail(const AffFrameArgs& fa, char* smem
                         }
                     }
                     // acquire: the siblings' partials are read after the count that announced them
-#ifndef SHASTA_AFF_NO_FENCE
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
                     if (poisoned) __hip_atomic_fetch_or(fa.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     cinv[511] = poisoned ? 1.0f : 0.0f;  // column 511 is never a column of matched2
                 }
@@ -370,7 +354,6 @@ __device__ __forceinline__ void ap_frame_tail(const AffFrameArgs& fa, char* smem
         }
         __syncthreads();
         if (i == 0) {
-            AP_STAMP(5);
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int col = h * AP_SCOLS + 4 * lane;
@@ -399,26 +382,21 @@ __device__ __forceinline__ void ap_frame_tail(const AffFrameArgs& fa, char* smem
                         if (col + e >= D) z[e] = 0.0f;  // the padding columns of `matched`
                     *reinterpret_cast<f32x4*>(a.matched + (size_t)(g0 + r) * a.ldm + col) = z;
                 }
-#ifndef AP_ABL_NO_M1  // ablation builds of tools/probes/aff_frame_probe.hip (results are wrong)
                 if (t < N && col < D) {
                     f32x4 e;
 #pragma unroll
                     for (int k = 0; k < 4; ++k) e[k] = ap_exp(v[k], cr) * inv;
                     ap_store4(a.m1 + ((size_t)b * N + t) * D + col, e, D - col);
                 }
-#endif
-#ifndef AP_ABL_NO_M2
                 if (col < N) {
                     f32x4 e;
 #pragma unroll
                     for (int k = 0; k < 4; ++k) e[k] = ap_exp(v[k], kc[h][k]) * ki[h][k];
                     ap_store4(fa.m2 + ((size_t)b * a.T + t) * N + col, e, N - col);
                 }
-#endif
             }
         }
     }
-    AP_STAMP(6);
 }
 
 }  // namespace shasta

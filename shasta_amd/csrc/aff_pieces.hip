@@ -22,7 +22,7 @@
 //    from the registers (per-wave partial max / sum through LDS, fixed order); the rows then pass through an fp32 staging
 //    [rows][256] in two column passes and leave as whole row segments (16-byte stores for `matched`, 8-byte stores for
 //    `matched1` = exp(x - max) / sum, four rows in flight per wave).
-//  Where a workgroup's time goes (tools/probes/aff_probe.hip, 128 rows, shader cycles): layer 1 56 k (MFMA 25 k, LDS reads 16 k
+//  Where a workgroup's time goes (in-kernel stamps of a probe removed after commit 96899a8, 128 rows, shader cycles): layer 1 56 k (MFMA 25 k, LDS reads 16 k
 //  and the cuts 15 k do not overlap: one barrier per chunk keeps the two waves of a SIMD in step), layers 2-5 31 k (latency of
 //  their weight loads and four barriers), layer 6 30 k (MFMA-bound), softmax statistics 30 k, output 61 k (20 k without the stores).
 #include "aff_frame.hpp"
@@ -33,9 +33,6 @@
 namespace shasta {
 
 typedef __bf16 qbf16x8 __attribute__((ext_vector_type(8)));
-#ifndef AP_PACE
-#define AP_PACE 4  // s_sleep units between the MFMA groups of layer 1 (see there)
-#endif
 
 __device__ __forceinline__ void ap_cut3(float a, float& h, float& m, float& l) {
     h = __uint_as_float(__float_as_uint(a) & 0xffff0000u);
@@ -160,7 +157,6 @@ __device__ __forceinline__ void ap_mlp(const AffPiecesArgs& a, char* smem, int g
     const int D = a.D;
     const qu32x4* wp = reinterpret_cast<const qu32x4*>(a.wp);
     const f32x16 zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    AP_STAMP(0);
 
     // ---- layer 1 (K = D -> 128): wave = (row block wid >> 1, feature blocks 2 (wid & 1) + {0, 1}).  Residual rows and weight
     // fragments reach LDS by LDS-DMA, each byte once per workgroup, in chunks of two k steps = 32 columns through a ring of NS
@@ -238,9 +234,9 @@ __device__ __forceinline__ void ap_mlp(const AffPiecesArgs& a, char* smem, int g
                 // (tools/gpu_ab.sh, alternating): 12.00 - 12.06 ms per step and 1075 W without the pauses against 11.52 - 11.65 ms
                 // and 1140 W with them (2, 4, 6 or 8 units of 64 cycles alike), although the kernel itself is 8 % shorter without.
                 ap_step(w0, x, acc0);
-                __builtin_amdgcn_s_sleep(AP_PACE);
+                __builtin_amdgcn_s_sleep(4);
                 ap_step(w1, x, acc1);
-                __builtin_amdgcn_s_sleep(AP_PACE);
+                __builtin_amdgcn_s_sleep(4);
             }
         };
 #pragma unroll
@@ -262,7 +258,6 @@ __device__ __forceinline__ void ap_mlp(const AffPiecesArgs& a, char* smem, int g
         ap_store_h<AP_AROW, AIMG>(HA, fb0 + 1, rb, lane, acc1, a.bias[0]);
     }
     __syncthreads();
-    AP_STAMP(1);
     const qu32x4* w2 = wp + ap_layer_offset(1, D) * 64;
     const qu32x4* w3 = wp + ap_layer_offset(2, D) * 64;
     const qu32x4* w4 = wp + ap_layer_offset(3, D) * 64;
@@ -296,7 +291,6 @@ __device__ __forceinline__ void ap_mlp(const AffPiecesArgs& a, char* smem, int g
         }
     }
     __syncthreads();
-    AP_STAMP(2);
     // ---- layer 6 (128 -> D): wave = feature blocks {wid + WAVES i} x the RB row blocks: 8 accumulators; every weight fragment
     // feeds RB x 6 MFMAs ----
     const int nfb = ap_fblocks(5, D);
@@ -320,7 +314,6 @@ __device__ __forceinline__ void ap_mlp(const AffPiecesArgs& a, char* smem, int g
             }
         }
     }
-    AP_STAMP(3);
 }
 
 template <int ROWS, int WAVES>
@@ -409,7 +402,6 @@ __global__ __launch_bounds__(64 * WAVES) void aff_pieces_kernel(AffPiecesArgs a)
         rmax[tid] = m;
         rinv[tid] = 1.0f / s;
     }
-    AP_STAMP(4);
     // ---- output: two passes of 8 feature blocks (256 columns) through the staging, whole row segments to global memory ----
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -462,7 +454,6 @@ __global__ __launch_bounds__(64 * WAVES) void aff_pieces_kernel(AffPiecesArgs a)
             }
         }
     }
-    AP_STAMP(5);
 }
 
 // aff_frame_kernel: the bf16-piece layers (ap_mlp) + the one-pass tail of aff_frame.hpp
@@ -543,13 +534,7 @@ int launch_aff_frame(const shasta_weights* w, const float* packed_pieces, const 
     a.ld = ld;
     a.ldm = ldm;
     fa.m2 = m2;
-#if defined(AP_SHAPE_64)
-    return launch_aff_frame_shape<64, 4>(fa, B, ws, st);
-#elif defined(AP_SHAPE_128)
-    return launch_aff_frame_shape<128, 8>(fa, B, ws, st);
-#else
     return B * cdiv(T, 128) >= 256 ? launch_aff_frame_shape<128, 8>(fa, B, ws, st) : launch_aff_frame_shape<64, 4>(fa, B, ws, st);
-#endif
 }
 
 int launch_aff_pieces(const shasta_weights* w, const float* packed_pieces, const float* residual, int ld, float* matched, int ldm,
@@ -570,15 +555,7 @@ int launch_aff_pieces(const shasta_weights* w, const float* packed_pieces, const
     a.ldm = ldm;
     // 128-row workgroups once they fill the 256 CUs (0.825 ms against 0.837 ms for 257 k rows); below that the 64-row shape puts
     // twice as many workgroups on the chip
-#if defined(AP_SHAPE_64) || defined(AP_SHAPE_128)  // probe builds only (tools/probes/aff_probe.hip): force one shape
-#ifdef AP_SHAPE_64
-    return launch_aff_pieces_shape<64, 4>(a, st);
-#else
-    return launch_aff_pieces_shape<128, 8>(a, st);
-#endif
-#else
     return cdiv(M, 128) >= 256 ? launch_aff_pieces_shape<128, 8>(a, st) : launch_aff_pieces_shape<64, 4>(a, st);
-#endif
 }
 
 }  // namespace shasta

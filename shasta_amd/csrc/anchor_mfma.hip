@@ -17,7 +17,7 @@
 // What limited it at 32/64 rows was VALU work between the MFMAs: the f32 MFMA runs at the vector rate and does not overlap
 // VALU instructions, so the 64-bit address arithmetic of every LDS-DMA instruction stretched a 2048-cycle tile to 2560
 // cycles.  The loop below is VALU-free (scalar base + 32-bit lane offset addressing); in-kernel stamps
-// (tools/probes/l1_clock_probe.hip) read 2200 cycles per tile at 64 rows = 93 % of the matrix pipe, at an in-kernel clock
+// (a clock-stamp build, removed after commit 96899a8) read 2200 cycles per tile at 64 rows = 93 % of the matrix pipe, at an in-kernel clock
 // of 1.98 GHz (32 rows: 1140 of 1024 cycles at 1.72 GHz - the chip lowers its clock under the combined HBM + MFMA load).  Split-K partials are reduced afterwards in a fixed order.
 #include "common.hpp"
 
@@ -37,9 +37,6 @@ struct AnchorMfmaArgs {
 
 // weights are read exactly once per launch: the weight stream is issued non-temporal (nt) so that the activation vectors
 // and the small weights of the following kernels stay resident in L2 / Infinity Cache (MI355X_MICROARCH.md, row nt-weights)
-#ifdef SHASTA_L1_STAMP
-__device__ unsigned long long g_l1_stamp[4096][3];
-#endif
 
 template <int N>
 __device__ __forceinline__ void wait_vm() {
@@ -177,9 +174,6 @@ __global__ __launch_bounds__(256) void anchor_l1_mfma_kernel(AnchorMfmaArgs a) {
         }
     };
 
-#ifdef SHASTA_L1_STAMP  // diagnostic build only (tools/probes/l1_clock_probe.hip): in-kernel clock and cycles per tile
-    const unsigned long long st0 = __builtin_amdgcn_s_memtime(), sr0 = __builtin_amdgcn_s_memrealtime();
-#endif
     // Prologue: fill the ring, fetch the fragments of tile 0.
     int issued = 0;
 #pragma unroll 1
@@ -234,13 +228,6 @@ __global__ __launch_bounds__(256) void anchor_l1_mfma_kernel(AnchorMfmaArgs a) {
         step(fb, fa, t + 1, std::false_type{});
     }
     if (t < NT) step(fa, fb, t, std::false_type{});
-#ifdef SHASTA_L1_STAMP
-    if (lane == 0 && wid == 0 && blockIdx.y == 0 && blockIdx.x < 4096) {
-        g_l1_stamp[blockIdx.x][0] = __builtin_amdgcn_s_memtime() - st0;
-        g_l1_stamp[blockIdx.x][1] = __builtin_amdgcn_s_memrealtime() - sr0;
-        g_l1_stamp[blockIdx.x][2] = (unsigned long long)NT;
-    }
-#endif
     // D[i = weight row][j = batch item]
     if constexpr (WIDE) {
         const int h = lane >> 5;

@@ -177,23 +177,17 @@ __device__ __forceinline__ uint32_t pack_h2(_Float16 even, _Float16 odd) {
     return __builtin_bit_cast(uint32_t, v);
 }
 
-// Experiment switch (-DSHASTA_L1_SHAPE16=1, tools/build_variant.py): the pre-cut fp16 form on v_mfma_f32_16x16x32_f16 instead of
+// Tried, and removed after commit 96899a8: the pre-cut fp16 form on v_mfma_f32_16x16x32_f16 instead of
 // v_mfma_f32_32x32x16_f16 - the same matrix cycles per tile (96 x 16 instead of 48 x 32 at 256 items per pass) and the same operand
 // bytes; tried because the chip can hold a higher clock on the 16 x 16 shape (MI355X_MICROARCH.md, DVFS give-back item 7).  Measured
 // (DESIGN.md section 4, K3a round 3): bit-for-bit the same sums are not expected (k = 32 per product instead of 2 x 16), results equal
 // within the pins; 1024 frame-pairs per step: weight stream 5.33 ms against 5.02 ms, and the pair kernel behind it 8.9 against 8.3 ms,
 // at 1170 W instead of 1280 W - slower at less power, so the 32 x 32 form stays.
-// Fragments of that shape: lane (i = lane & 15, kb = lane >> 4) holds row / item i, k = 8 kb .. 8 kb + 7 of a 32-wide k tile.
-#ifndef SHASTA_L1_SHAPE16
-#define SHASTA_L1_SHAPE16 0
-#endif
-constexpr bool kPrecutShape16 = SHASTA_L1_SHAPE16 != 0;
 
 struct SplitXArgs {
     const float* x[2];
-    uint32_t* xs;  // [2 frames][NBLK][KT][XT][2 k-steps (shape16: 16-item halves)][NP pieces][64 lanes][8 bf16 / fp16]
+    uint32_t* xs;  // [2 frames][NBLK][KT][XT][2 k-steps][NP pieces][64 lanes][8 bf16 / fp16]
     int B, KT, NBLK, XT, x_batch_stride, NP;
-    int shape16;   // NP = 2 only: fragments for v_mfma_f32_16x16x32_f16 (the pre-cut weight stream)
     const unsigned* xmax;  // NP = 2: [2 frames][B] row maxima (row_max_kernel): batch row b of frame f is cut as x * 2^e, e = its range exponent
 };
 
@@ -216,9 +210,9 @@ __global__ __launch_bounds__(256) void split_x_kernel(SplitXArgs a) {
     for (int i = threadIdx.x; i < 1024; i += 256) {
         const int lane = i & 63, s = (i >> 6) & 1, ktl = i >> 7;
         if (ktl >= nkt) continue;
-        // 32x32x16 fragments: (item r, k half h) of k step s; 16x16x32: (item 16 s + i, k block kb) of the whole tile
-        const int r = a.shape16 ? 16 * s + (lane & 15) : lane & 31, h = lane >> 5;
-        const float* p = a.shape16 ? &tile[r][ktl * 32 + 8 * (lane >> 4)] : &tile[r][ktl * 32 + 16 * s + 8 * h];
+        // 32x32x16 fragments: (item r, k half h) of k step s
+        const int r = lane & 31, h = lane >> 5;
+        const float* p = &tile[r][ktl * 32 + 16 * s + 8 * h];
         const f32x4 v0 = *reinterpret_cast<const f32x4*>(p), v1 = *reinterpret_cast<const f32x4*>(p + 4);
         const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
         if (a.NP == 2) {
@@ -259,7 +253,7 @@ __global__ __launch_bounds__(256) void split_x_kernel(SplitXArgs a) {
 // ---- pre-cut weight image (SHASTA_OPT_PRECUT_WEIGHT_STREAM) ---------------------------------------------------------------------
 // The fp16 form cuts every fp32 weight into its two pieces on the VALU, between the MFMAs, once per BATCH BLOCK (twice per step at
 // 512 frame-pairs).  The image holds the pieces instead: per (MLP, 32-row group, 32-wide k tile) one 4 KB block =
-// [k step 2 (shape16: 16-row half)][piece 2][lane 64][8 fp16] - exactly the four A-operand fragments of a wave, in lane order - i.e. the same 4 bytes per
+// [k step 2][piece 2][lane 64][8 fp16] - exactly the four A-operand fragments of a wave, in lane order - i.e. the same 4 bytes per
 // weight on the stream, +4.1 GB resident next to the fp32 checkpoint tensors at N=500, and nothing but LDS-DMA, ds_read and MFMA
 // in the loop.  Built by shasta_aug_shape_aux_f32 behind the row maxima; rebuilt when the weights change, like them.
 struct PrecutArgs {
@@ -281,11 +275,11 @@ __global__ __launch_bounds__(256) void precut_weights_kernel(PrecutArgs a) {
     }
     __syncthreads();
     const int lane = threadIdx.x & 63;
-    for (int f = threadIdx.x >> 6; f < 2 * nkt; f += 4) {  // (k tile, k step / row half) pairs, one per wave
+    for (int f = threadIdx.x >> 6; f < 2 * nkt; f += 4) {  // (k tile, k step) pairs, one per wave
         const int ktl = f >> 1, sstep = f & 1;
-        const int frow = kPrecutShape16 ? 16 * sstep + (lane & 15) : lane & 31;
+        const int frow = lane & 31;
         const int wex = range_exponent_bits(a.wmax[mlp * a.H + min(g * 32 + frow, a.H - 1)]);
-        const float* p = kPrecutShape16 ? &tile[frow][ktl * 32 + 8 * (lane >> 4)] : &tile[frow][ktl * 32 + 16 * sstep + 8 * (lane >> 5)];
+        const float* p = &tile[frow][ktl * 32 + 16 * sstep + 8 * (lane >> 5)];
         u32x4 hi, lo;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -323,13 +317,6 @@ struct AnchorSplitArgs {
     const unsigned* wmax;  // NP = 2: [4][H] maxima of the weight rows (launch_w_maxima, pack time)
 };
 
-#ifdef SHASTA_L1_STAMP  // diagnostic build only (tools/probes/l1_split_probe.hip): in-kernel clock and cycles per tile
-__device__ unsigned long long g_split_stamp[4096][3];
-#endif
-#ifdef SHASTA_L1_TIMELINE  // diagnostic build only (tools/l1_timeline.py): when and where every workgroup ran
-__device__ unsigned long long g_split_timeline[4096][4];  // {shader cycles, s_memrealtime at start, at end, XCC_ID << 32 | HW_ID}
-#endif
-
 template <int N>
 __device__ __forceinline__ void wait_vm_split() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -340,14 +327,13 @@ template <int XT, int NS, int NP, bool PRECUT = false>
 __global__ __launch_bounds__(256) void anchor_l1_split_kernel(AnchorSplitArgs a) {
     static_assert(!PRECUT || NP == 2, "the pre-cut image holds fp16 pieces");
     constexpr int NPROD = NP == 3 ? 6 : 3;
-    constexpr bool S16 = PRECUT && kPrecutShape16;  // experiment: 16x16x32 fragments and accumulators (the comment at SHASTA_L1_SHAPE16)
     constexpr int XCH = 2 * NP * XT;             // 1 KB fragments of one x tile
     constexpr int XPW = XCH / 4;                 // of which every wave fetches this many
     static_assert(XCH % 4 == 0, "x fragments are dealt to four waves");
     constexpr int SLOT = 4 * 1024 + XCH * 256;   // dwords per ring slot: 4 private W tiles + the shared x tile
     constexpr int PER_TILE = 4 + XPW;            // vmcnt units a wave spends per tile
     static_assert(PER_TILE * (NS - 1) <= 63, "vmcnt is 6 bits");
-    constexpr int NM = (S16 ? 4 : 2) * NPROD * XT;  // MFMAs per tile
+    constexpr int NM = 2 * NPROD * XT;  // MFMAs per tile
     constexpr int ND = PER_TILE;                 // LDS-DMA instructions per tile and wave
     constexpr int NR = 4 + XCH;                  // ds_read_b128 per tile and wave
     constexpr int SG = PRECUT ? 1 : (NM - 8) / 16;  // MFMA gaps between two weight elements being cut
@@ -412,8 +398,8 @@ __global__ __launch_bounds__(256) void anchor_l1_split_kernel(AnchorSplitArgs a)
     };
 
     struct Frag {
-        u32x4 A[2][NP];      // weight pieces [k-step (S16: 16-row half)][piece]
-        u32x4 X[XT][2][NP];  // activation pieces [32-item block][k-step (S16: 16-item half)][piece]
+        u32x4 A[2][NP];      // weight pieces [k-step][piece]
+        u32x4 X[XT][2][NP];  // activation pieces [32-item block][k-step][piece]
     };
     f32x4 raw[4];           // fp32 weights of the tile being cut: [2 * k-step + half]
     const int frow = lane & 31, fh = lane >> 5, fsw = (frow >> 1) & 7;
@@ -462,42 +448,22 @@ __global__ __launch_bounds__(256) void anchor_l1_split_kernel(AnchorSplitArgs a)
         }
     };
 
-    f32x16 acc[S16 ? 1 : XT];
-    f32x4 acc4[S16 ? XT : 1][2][2];  // S16: the four 16 x 16 blocks [item half c][row half rb] of every 32 x 32 block
+    f32x16 acc[XT];
 #pragma unroll
-    for (int u = 0; u < (S16 ? 1 : XT); ++u) acc[u] = f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int u = 0; u < (S16 ? XT : 1); ++u)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc4[u][c >> 1][c & 1] = f32x4{0, 0, 0, 0};
+    for (int u = 0; u < XT; ++u) acc[u] = f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     // piece products, small to large
     constexpr int PW[6] = {2, 0, 1, 1, 0, 0}, PW2[3] = {1, 0, 0};
     constexpr int PX[6] = {0, 2, 1, 0, 1, 0}, PX2[3] = {0, 1, 0};
     auto mma_one = [&](const Frag& f, int i) {
-        if constexpr (S16) {
-            // per 32-item block (its fragments die as the next tile's arrive, as in the 32 x 32 form): product-major over the block's
-            // four accumulators, so the three products of an accumulator (small to large, as above) are four instructions apart
-            const int u = i / (4 * NPROD), pr = (i % (4 * NPROD)) >> 2, c = (i >> 1) & 1, rb = i & 1;
-            acc4[u][c][rb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, f.A[rb][PW2[pr]]),
-                                                                    __builtin_bit_cast(f16x8, f.X[u][c][PX2[pr]]), acc4[u][c][rb], 0, 0, 0);
-            return;
-        } else {
         const int s = i / (NPROD * XT), u = (i / NPROD) % XT, pr = i % NPROD;
-#ifdef SPLIT_EXP_NOMFMA  // probe: data movement only
-        if (i % NPROD != 0) return;
-#endif
         if constexpr (NP == 3)
             acc[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f.A[s][PW[pr]]),
                                                              __builtin_bit_cast(bf16x8, f.X[u][s][PX[pr]]), acc[u], 0, 0, 0);
         else
             acc[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, f.A[s][PW2[pr]]),
                                                             __builtin_bit_cast(f16x8, f.X[u][s][PX2[pr]]), acc[u], 0, 0, 0);
-        }
     };
 
-#if defined(SHASTA_L1_STAMP) || defined(SHASTA_L1_TIMELINE)
-    const unsigned long long st0 = __builtin_amdgcn_s_memtime(), sr0 = __builtin_amdgcn_s_memrealtime();
-#endif
     // Prologue: fill the ring, take tile 0 into registers.
     {
         int s = 0;
@@ -527,9 +493,7 @@ __global__ __launch_bounds__(256) void anchor_l1_split_kernel(AnchorSplitArgs a)
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // my reads of tile t's slot have retired
                 if constexpr (STEADY) wait_vm_split<PER_TILE*(NS - 2)>();
                 else wait_vm_split<0>();
-#ifndef SPLIT_EXP_NOBAR  // probe: no workgroup coupling (results are wrong)
                 __builtin_amdgcn_s_barrier();
-#endif
                 if constexpr (!STEADY) {
                     if (t + NS < NT) issue(t + NS, sc);
                 }
@@ -566,40 +530,10 @@ __global__ __launch_bounds__(256) void anchor_l1_split_kernel(AnchorSplitArgs a)
     }
     if (t < NT) step(fa, fb, t, sc, std::false_type{});
 
-#ifdef SHASTA_L1_STAMP
-    if (lane == 0 && wid == 0 && bblk == 0 && blockIdx.x < 4096) {
-        g_split_stamp[blockIdx.x][0] = __builtin_amdgcn_s_memtime() - st0;
-        g_split_stamp[blockIdx.x][1] = __builtin_amdgcn_s_memrealtime() - sr0;
-        g_split_stamp[blockIdx.x][2] = (unsigned long long)NT;
-    }
-#endif
-#ifdef SHASTA_L1_TIMELINE
-    if (lane == 0 && wid == 0 && blockIdx.x < 4096) {
-        g_split_timeline[blockIdx.x][0] = __builtin_amdgcn_s_memtime() - st0;
-        g_split_timeline[blockIdx.x][1] = sr0;
-        g_split_timeline[blockIdx.x][2] = __builtin_amdgcn_s_memrealtime();
-        g_split_timeline[blockIdx.x][3] = ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) | __builtin_amdgcn_s_getreg((31 << 11) | 4);
-    }
-#endif
     // D[i = weight row][j = batch row]
-    if constexpr (S16) {  // 16 x 16 blocks: lane = (item lane & 15, rows 4 (lane >> 4) .. + 3)
+    if (active) {
 #pragma unroll
         for (int u = 0; u < XT; ++u) {
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const int b = (bblk * XT + u) * 32 + 16 * c + (lane & 15);
-                if (b >= a.B || !active) continue;
-                float* o = a.part + ((size_t)ks * a.B + b) * (4 * a.H) + mlp * a.H;
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    const int row = r0 + 16 * (r >> 2) + 4 * (lane >> 4) + (r & 3);
-                    if (row < a.H) o[row] = acc4[u][c][r >> 2][r & 3];
-                }
-            }
-        }
-    } else if (active) {
-#pragma unroll
-        for (int u = 0; u < (S16 ? 1 : XT); ++u) {
             const int b = (bblk * XT + u) * 32 + frow;
             if (b < a.B) {
                 float* o = a.part + ((size_t)ks * a.B + b) * (4 * a.H) + mlp * a.H;
@@ -626,7 +560,7 @@ __global__ __launch_bounds__(256) void anchor_l1_split_kernel(AnchorSplitArgs a)
 //    4 KB / 64 KB blocks are k-step-major resp. hold whole fragments: a slot takes 1 KB fragments wherever they lie).
 // Per accumulator the products arrive in the order of the 256-item kernel (k steps ascending; w_l x_h, w_h x_l, w_h x_h).
 // Counters (profiles/r05_pmc_*): the matrix pipe is 85 % busy in CYCLES (76 % in the 256-item form); what still moves the kernel is the
-// CLOCK the chip holds at its power cap: ablation builds (WIDE_EXP_*) run at 1.82 GHz without the ds_reads, 1.62 GHz without the
+// CLOCK the chip holds at its power cap: ablation builds (removed after commit 96899a8) run at 1.82 GHz without the ds_reads, 1.62 GHz without the
 // LDS-DMA, 1.45 GHz with everything (under the profiler).  A four-wave form with 128 x 128 register tiles whose activation fragments
 // go from L2 straight into registers (32 KB of ds_read per k step instead of 96) was built and measured: correct, but one wave per SIMD
 // leaves the pipe 76 % busy and the launch 3 % longer (LABNOTES section 12; git history: anchor_l1_direct_kernel).
@@ -692,9 +626,6 @@ __global__ __launch_bounds__(512) void anchor_l1_wide_kernel(AnchorSplitArgs a) 
     constexpr int PW2[3] = {1, 0, 0}, PX2[3] = {0, 1, 0};  // piece products, small to large
     auto mma_one = [&](const Frag& f, int i) {             // product-major: eight independent accumulators between two products of one
         const int pr = i >> 3, j = (i >> 2) & 1, u = i & 3;
-#ifdef WIDE_EXP_NOMFMA  // probe: data movement only
-        if (pr != 0) return;
-#endif
         acc[j][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, f.A[j][PW2[pr]]), __builtin_bit_cast(f16x8, f.X[u][PX2[pr]]),
                                                            acc[j][u], 0, 0, 0);
     };
@@ -726,9 +657,7 @@ __global__ __launch_bounds__(512) void anchor_l1_wide_kernel(AnchorSplitArgs a) 
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // my reads of step t's slot have retired
                 if constexpr (STEADY) wait_vm_split<ND*(NS - 2)>();
                 else wait_vm_split<0>();
-#ifndef WIDE_EXP_NOBAR  // probe: no workgroup coupling (results are wrong)
                 __builtin_amdgcn_s_barrier();
-#endif
                 if constexpr (!STEADY) {
                     if (t + NS < NT) {
 #pragma unroll
@@ -736,14 +665,10 @@ __global__ __launch_bounds__(512) void anchor_l1_wide_kernel(AnchorSplitArgs a) 
                     }
                 }
             }
-#ifndef WIDE_EXP_NODMA  // probe: the ring is never refilled (results are wrong)
             if (i >= 1 && i - 1 < ND) {
                 if constexpr (STEADY) dma(t + NS, sc, i - 1);
             }
-#endif
-#ifndef WIDE_EXP_NOREAD  // probe: the fragments of the first k step for ever (results are wrong)
             if (i >= 1 && i - 1 < NR) read_one(sn, nxt, i - 1);
-#endif
             __builtin_amdgcn_sched_barrier(0);
         }
     };
@@ -786,7 +711,7 @@ __global__ __launch_bounds__(512) void anchor_l1_wide_kernel(AnchorSplitArgs a) 
 }
 
 // the wide form serves the pre-cut fp16 stream whenever 512-item passes pad the batch no more than 256-item passes do
-static inline bool split_wide(int B, int np, bool precut) { return np == 2 && precut && !kPrecutShape16 && B > 256 && cdiv(B, 512) * 512 <= cdiv(B, 256) * 256; }
+static inline bool split_wide(int B, int np, bool precut) { return np == 2 && precut && B > 256 && cdiv(B, 512) * 512 <= cdiv(B, 256) * 256; }
 
 // np = pieces per operand: 3 = bf16 (six products), 2 = fp16 (three products, SHASTA_OPT_F16X2_WEIGHT_STREAM)
 // np == 2 without the pre-cut image is used above 64 rows only; with it, 32 / 64 items per pass serve the smaller batches too
@@ -819,7 +744,6 @@ void launch_split_x(const float* feat, const float* prev_feat, void* xs, int K, 
     sx.XT = XT;
     sx.x_batch_stride = x_batch_stride;
     sx.NP = np;
-    sx.shape16 = np == 2 && precut && kPrecutShape16;
     sx.xmax = xmax;
     hipLaunchKernelGGL(split_x_kernel, dim3(cdiv(KT, 8), NBLK * XT, 2), dim3(256), 0, st, sx);
 }
@@ -879,11 +803,7 @@ void launch_anchor_l1_split(const float* const W[4], const void* xs, float* part
     };
     if (wide) {
         const size_t ldsb = (size_t)4 * (8 + 2 * 16) * 1024;  // four slots of 40 KB: all of the CU's LDS
-#ifdef WIDE_EXP_NS3
-        if (false) {
-#else
         if (hipFuncSetAttribute((const void*)anchor_l1_wide_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb) == hipSuccess) {
-#endif
             hipLaunchKernelGGL(anchor_l1_wide_kernel<4>, dim3(2 * a.KS * quads * NBLK), dim3(512), ldsb, st, a);
         } else {  // a device that grants less: three slots
             (void)hipGetLastError();
@@ -904,9 +824,3 @@ void launch_anchor_l1_split(const float* const W[4], const void* xs, float* part
 }
 
 }  // namespace shasta
-
-#ifdef SHASTA_L1_TIMELINE
-extern "C" __attribute__((visibility("default"))) int shasta_debug_l1_timeline(unsigned long long* out) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(shasta::g_split_timeline), sizeof(shasta::g_split_timeline));
-}
-#endif

@@ -88,14 +88,6 @@ int embed_pack(const shasta_weights* w, float* packed, hipStream_t st) {
     return check_launch("embed_pack");
 }
 
-#ifdef SHASTA_EMBED_STAMP  // diagnostic build only (tools/probes/embed_probe.hip)
-__device__ unsigned long long g_embed_stamp[4096][8];
-#define ER_STAMP(i) \
-    if (threadIdx.x == 0 && blockIdx.y == 0 && blockIdx.x < 4096) g_embed_stamp[blockIdx.x][i] = __builtin_amdgcn_s_memtime()
-#else
-#define ER_STAMP(i)
-#endif
-
 struct EmbedArgs {
     const float* x[2];     // [0] prev feature table, [1] current: (M, F) rows
     const float* tab[2];   // box tables (M, 8)
@@ -129,7 +121,6 @@ __global__ __launch_bounds__(64 * ER_WAVES) void embed_rows_kernel(EmbedArgs a) 
     const PairDims d(F);
     const PackedLayout P(a.N, a.nf, F);
     const int ES = d.ET + 8;  // staging row stride (floats): the row's values, then its 8 box floats
-    ER_STAMP(0);
     float* wT = reinterpret_cast<float*>(smem + max(NS * S::SLOT, ER_ROWS * ES * 4));  // [7][104] box-column weights, transposed
     {
         const float* wb = a.packed + (side ? P.wbox_cur : P.wbox_prev);
@@ -214,8 +205,7 @@ __global__ __launch_bounds__(64 * ER_WAVES) void embed_rows_kernel(EmbedArgs a) 
                     for (int fb = 0; fb < NFB; ++fb) acc[fb] = ER_MFMA(w[st][fb][PWI[pr]], x[PXI[pr]], acc[fb]);
             }
         };
-        ER_STAMP(1);
-        // tools/probes/embed_probe.hip: 37 k cycles per workgroup in this loop, 18 k of them MFMA time; launch time with parts removed
+        // in-kernel stamps (a probe removed after commit 96899a8): 37 k cycles per workgroup in this loop, 18 k of them MFMA time; launch time with parts removed
         // (timing only): 0.250 ms -> 0.195 without five of the six MFMAs, 0.232 with the rows always from one cached chunk, 0.245
         // with a third of the fragment reads, 0.246 without the barrier.
 #pragma unroll
@@ -232,7 +222,6 @@ __global__ __launch_bounds__(64 * ER_WAVES) void embed_rows_kernel(EmbedArgs a) 
             slot = slot == NS - 1 ? 0 : slot + 1;
         }
     }
-    ER_STAMP(2);
     __syncthreads();  // the staging lies over the ring
     float* xs = reinterpret_cast<float*>(smem);
     {
@@ -247,7 +236,6 @@ __global__ __launch_bounds__(64 * ER_WAVES) void embed_rows_kernel(EmbedArgs a) 
         *reinterpret_cast<f32x4*>(xs + (tid >> 1) * ES + d.ET + 4 * (tid & 1)) = mybox;
     }
     __syncthreads();
-    ER_STAMP(3);
     // rows: 32 threads per row, a float4 of outputs per thread and pass (ET <= 128: one pass)
     const int q = tid & 31;
     // this thread's columns 4 q (and 4 q + 128 when ET > 128) are the same for every row: their bias is loaded once
@@ -335,7 +323,6 @@ __global__ __launch_bounds__(64 * ER_WAVES) void embed_rows_kernel(EmbedArgs a) 
             }
         }
     }
-    ER_STAMP(4);
 }
 
 bool embed_rows_serves(int F) { return F == 64 || F == 256 || F == 320; }
@@ -371,11 +358,7 @@ int launch_embed_rows(const shasta_weights* w, const float* packed, const float*
     switch ((P.E12 + 31) / 32) {
         case 2: return launch_embed_shape<2, 256, 8, 0>(a, st);
         case 3: return launch_embed_shape<3, 128, 4, 2>(a, st);  // F = 256: two workgroups per CU
-#ifdef SHASTA_ER_F320_128  // experiment (tools/build_variant.py): 128-row workgroups at F = 320 too - 83 KB each, still one per CU: 81 - 82 us against 75 - 77 at the car tables x 512
-        case 4: return launch_embed_shape<4, 128, 4, 2>(a, st);
-#else
-        case 4: return launch_embed_shape<4, 256, 8, 0>(a, st);
-#endif
+        case 4: return launch_embed_shape<4, 256, 8, 0>(a, st);  // (128-row workgroups here too - 83 KB each, still one per CU - measured 81 - 82 us against 75 - 77 at the car tables x 512)
     }
     set_error_msg("embed_rows: unsupported feat_dim");
     return SHASTA_E_ARG;

@@ -199,9 +199,6 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_quad_kernel(GemmNtQuad p, int
 // order at the end.  Preconditions (launch_gemm_nt_quad checks them): K % 4 == 0, 16-byte aligned operand rows.  Measured at
 // N = 500: 50 us against 94 us for the 64 x 64 tiles at 512 rows; at 64 rows 36 - 41 us, no better than the VALU kernels of the small
 // batches (anchor.hip: 37 - 40 us), which therefore stay below 256 rows.
-#ifndef SHASTA_GEMM_DIRECT
-#define SHASTA_GEMM_DIRECT 1
-#endif
 __global__ __launch_bounds__(256) void gemm_nt_f32_direct_quad_kernel(GemmNtQuad p, int lda, int ldw, int ldc, int M, int N, int K, int act) {
     __shared__ float red[4][32][33];
     const int z = blockIdx.z;
@@ -261,7 +258,7 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_direct_quad_kernel(GemmNtQuad
 
 // true when launch_gemm_nt_quad will take the direct form for these operands
 bool gemm_nt_quad_direct_ok(const float* const A[4], const float* const W[4], int lda, int ldw, int K) {
-    bool ok = SHASTA_GEMM_DIRECT && lda % 4 == 0 && ldw % 4 == 0 && K % 4 == 0 && K >= 512;
+    bool ok = lda % 4 == 0 && ldw % 4 == 0 && K % 4 == 0 && K >= 512;
     for (int i = 0; i < 4; ++i) ok = ok && (((uintptr_t)A[i] | (uintptr_t)W[i]) % 16 == 0);
     return ok;
 }
@@ -277,7 +274,7 @@ int launch_gemm_nt_quad(const float* const A[4], const float* const W[4], const 
         p.C[i] = C[i];
         vec = vec && (((uintptr_t)A[i] | (uintptr_t)W[i]) % 16 == 0);
     }
-    if (SHASTA_GEMM_DIRECT && vec && K % 4 == 0 && K >= 512) {  // skinny, long K: the direct form
+    if (vec && K % 4 == 0 && K >= 512) {  // skinny, long K: the direct form
         hipLaunchKernelGGL(gemm_nt_f32_direct_quad_kernel, dim3(cdiv(N, 32), cdiv(M, 32), 4), dim3(256), 0, st, p, lda, ldw, ldc, M, N, K, act);
         return check_launch("gemm_nt_f32_direct_quad");
     }

@@ -69,9 +69,6 @@ constexpr size_t pb_lds_bytes(bool bwd) {
 }
 
 #define PB_MFMA4(a, b, c) __builtin_amdgcn_mfma_f32_4x4x1f32((a), (b), (c), 0, 0, 0)
-#ifndef PB_ABL  // ablation builds only (tools/time_pair_mlp.py; wrong results): 1 no weight-gradient MFMAs, 2 no W2^T g2, 4 no sum over the lanes
-#define PB_ABL 0
-#endif
 
 // W2 (E2, E1), W3 (E3, E2), W4 (E4, E3): torch's nn.Linear layout; b2, b3, b4 their biases (W4, b4 unused when E4 == 0)
 template <class M, bool BWD>
@@ -262,7 +259,7 @@ __global__ __launch_bounds__(64 * PB_WPB) void pair_mlp_kernel(const float* __re
         }
         // ---- weight / bias gradients: sum over the 64 pairs of the tile on the matrix pipe ----
 #pragma unroll 4
-        for (int s = 0; s < ((PB_ABL & 1) ? 0 : 16); ++s) {
+        for (int s = 0; s < 16; ++s) {
             float av[MB], bv[NBH];
 #pragma unroll
             for (int mb = 0; mb < MB; ++mb) av[mb] = L[16 * mb * RS + ka + 4 * s];
@@ -282,7 +279,7 @@ __global__ __launch_bounds__(64 * PB_WPB) void pair_mlp_kernel(const float* __re
 #pragma unroll
             for (int j = 0; j < IG; ++j) gh[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-            for (int og = 0; og < ((PB_ABL & 2) ? 0 : KG2); ++og) {
+            for (int og = 0; og < KG2; ++og) {
                 f32x4 a[IG];
 #pragma unroll
                 for (int j = 0; j < IG; ++j) a[j] = *reinterpret_cast<const f32x4*>(trow + M::T2B + ((ib0 + j) * KG2 + og) * 16);
@@ -309,7 +306,7 @@ __global__ __launch_bounds__(64 * PB_WPB) void pair_mlp_kernel(const float* __re
                 const f32x4* row = reinterpret_cast<const f32x4*>(L + (32 + M::H1 + r0 + lane) * RS);
                 f32x4 s4 = {0.0f, 0.0f, 0.0f, 0.0f};  // four chains, combined in a fixed order
 #pragma unroll
-                for (int j = 0; j < ((PB_ABL & 4) ? 1 : 16); ++j) s4 += row[j];
+                for (int j = 0; j < 16; ++j) s4 += row[j];
                 gup_part[(((size_t)dt * B + b) * T + t) * E1 + r0 + lane] = (s4[0] + s4[1]) + (s4[2] + s4[3]);
             }
         }

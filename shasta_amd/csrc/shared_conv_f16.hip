@@ -150,7 +150,7 @@ struct Conv16Args {
 
 // PB = 32-pixel blocks per wave.  PB = 1: 8 waves (two per SIMD), each 32 pixels x 64 channels.  PB = 2: 4 waves (one per SIMD, up to 512
 // registers), each 64 pixels x 64 channels: every weight fragment read from LDS feeds two pixel blocks (0.67 instead of 1 ds_read_b128
-// per MFMA) and no other wave's vector instructions compete with a wave's matrix instructions for issue slots.
+// per MFMA) and no other wave's vector instructions compete with a wave's matrix instructions for issue slots.  The launcher uses PB = 1.
 template <int PB>
 __global__ __launch_bounds__(512 / PB, PB == 1 ? 2 : 1) void shared_conv_f16_kernel(Conv16Args a) {
     constexpr int NW = 8 / PB;            // waves per workgroup
@@ -221,20 +221,13 @@ __global__ __launch_bounds__(512 / PB, PB == 1 ? 2 : 1) void shared_conv_f16_ker
             const char* xj = uniform_ptr(xc + (size_t)j * npix * 4);
 #pragma unroll
             for (int it = 0; it < NIT; ++it) {
-#ifdef C16_DBG_CLOADS
-                r[it][j] = *reinterpret_cast<const float*>(xj + ld_off[it]);
-#else
                 asm volatile("global_load_dword %0, %1, %2" : "=v"(r[it][j]) : "v"(ld_off[it]), "s"(xj) : "memory");
-#endif
             }
         }
     };
     // wait until at most `left` of this wave's youngest vector-memory operations are in flight, and tie r[] to the wait so that
     // nothing reads a register before it has landed
     auto wait_tile = [&](auto left) __attribute__((always_inline)) {
-#if defined(C16_DBG_WAIT0) || defined(C16_DBG_CLOADS)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
         asm volatile("s_waitcnt vmcnt(%8)"
                      : "+v"(r[0][0]), "+v"(r[0][1]), "+v"(r[0][2]), "+v"(r[0][3]), "+v"(r[0][4]), "+v"(r[0][5]), "+v"(r[0][6]), "+v"(r[0][7])
                      : "n"(decltype(left)::value));
@@ -260,9 +253,7 @@ __global__ __launch_bounds__(512 / PB, PB == 1 ? 2 : 1) void shared_conv_f16_ker
         constexpr int IB = 2 * C16_WBUF + decltype(bufc)::value * C16_INBUF;
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
-#ifndef C16_DBG_NOSKIP
             if (!item_live[it]) continue;  // wave-uniform
-#endif
             w32x4 hi, lo;
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj) {  // 2.5 vector instructions per value: packed scale, packed convert, two exact residuals, packed convert
@@ -311,10 +302,6 @@ __global__ __launch_bounds__(512 / PB, PB == 1 ? 2 : 1) void shared_conv_f16_ker
         f.b1l = *reinterpret_cast<const h16x8*>(wb + (tap * 4 + 3) * 1024);
     };
     auto mma_tap = [&](const Frag& f) __attribute__((always_inline)) {  // piece products, small to large
-#ifdef C16_ABL_NO_MFMA  // ablation build (tools/build_variant.py): everything but the matrix instructions; results are wrong
-        asm volatile("" ::"v"(f.ah[0]), "v"(f.al[0]), "v"(f.b0h), "v"(f.b0l), "v"(f.b1h), "v"(f.b1l));
-        return;
-#endif
 #pragma unroll
         for (int pb = 0; pb < PB; ++pb) {
             acc[pb][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.al[pb], f.b0h, acc[pb][0], 0, 0, 0);
@@ -362,9 +349,7 @@ __global__ __launch_bounds__(512 / PB, PB == 1 ? 2 : 1) void shared_conv_f16_ker
         constexpr int CUT = decltype(cut_after)::value, CUR = decltype(bufc)::value;
         using NXT = std::integral_constant<int, CUR ^ 1>;
         const int nxt = min(ch + 1, nchunk - 1), nx2 = min(ch + 2, nchunk - 1);
-#ifndef C16_ABL_NO_DMA
         dma_weights(nxt, CUR ^ 1, ndma);
-#endif
         Frag fa, fb;
         read_tap(bufc, 0, fa);
 #pragma unroll
@@ -373,11 +358,9 @@ __global__ __launch_bounds__(512 / PB, PB == 1 ? 2 : 1) void shared_conv_f16_ker
             mma_tap(fa);
             if (tap + 1 == CUT) {
                 __builtin_amdgcn_sched_barrier(0);  // (the scheduler otherwise lifts the cut - and its wait for the loads - to the top of the trip)
-#ifndef C16_ABL_NO_STAGE
                 wait_tile(ndma);
                 cut_store(NXT{});
                 load_chunk(nx2);
-#endif
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (tap + 1 < 9) {
@@ -385,35 +368,17 @@ __global__ __launch_bounds__(512 / PB, PB == 1 ? 2 : 1) void shared_conv_f16_ker
                 mma_tap(fb);
                 if (tap + 2 == CUT) {
                     __builtin_amdgcn_sched_barrier(0);
-#ifndef C16_ABL_NO_STAGE
                     wait_tile(ndma);
                     cut_store(NXT{});
                     load_chunk(nx2);
-#endif
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
         }
-#ifdef C16_ABL_NO_STAGE
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#else
-#if defined(C16_DBG_WAIT0) || defined(C16_DBG_CLOADS)
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#else
         asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NLD) : "memory");
-#endif
-#endif
-#ifndef C16_ABL_NO_BARRIER
         __builtin_amdgcn_s_barrier();
-#endif
         asm volatile("" ::: "memory");
     };
-#ifndef C16_CUT_A
-#define C16_CUT_A 2
-#endif
-#ifndef C16_CUT_B
-#define C16_CUT_B 6
-#endif
     auto all_chunks = [&](auto cut_after, auto ndma) __attribute__((always_inline)) {
         int ch = 0;
 #pragma unroll 1
@@ -423,8 +388,8 @@ __global__ __launch_bounds__(512 / PB, PB == 1 ? 2 : 1) void shared_conv_f16_ker
         }
         if (ch < nchunk) chunk(ch, B0{}, cut_after, ndma);
     };
-    if (wv < NSPLIT) all_chunks(std::integral_constant<int, C16_CUT_A>{}, std::integral_constant<int, NDMA_LO>{});
-    else all_chunks(std::integral_constant<int, C16_CUT_B>{}, std::integral_constant<int, NDMA_HI>{});
+    if (wv < NSPLIT) all_chunks(std::integral_constant<int, 2>{}, std::integral_constant<int, NDMA_LO>{});
+    else all_chunks(std::integral_constant<int, 6>{}, std::integral_constant<int, NDMA_HI>{});
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the staged-again last chunk: nothing may be in flight when the wave ends
 
     // epilogue: D[pixel][channel]: lane = channel (32 nb + li), pixel = (r & 3) + 8 (r >> 2) + 4 h of the block's 32
@@ -603,10 +568,6 @@ __global__ __launch_bounds__(512, 2) void shared_conv_f16w_kernel(Conv16Args a) 
         f.b1l = *reinterpret_cast<const h16x8*>(wb + (tap * 4 + 3) * 1024);
     };
     auto mma_tap = [&](const Frag& f) __attribute__((always_inline)) {  // piece products, small to large
-#ifdef W2_ABL_NO_MFMA
-        asm volatile("" ::"v"(f.ah[0]), "v"(f.al[0]), "v"(f.ah[1]), "v"(f.al[1]), "v"(f.b0h), "v"(f.b0l), "v"(f.b1h), "v"(f.b1l));
-        return;
-#endif
 #pragma unroll
         for (int pb = 0; pb < PB; ++pb) {
             acc[pb][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.al[pb], f.b0h, acc[pb][0], 0, 0, 0);
@@ -654,12 +615,8 @@ __global__ __launch_bounds__(512, 2) void shared_conv_f16w_kernel(Conv16Args a) 
         auto stage = [&]() __attribute__((always_inline)) {
             __builtin_amdgcn_sched_barrier(0);
             wait_tile(std::integral_constant<int, 2>{});  // everything but the two fragments this wave requested last
-#ifndef W2_ABL_NO_CUT   // ablation builds (tools/build_variant.py; results are wrong)
             cut_store(NXT{});
-#endif
-#ifndef W2_ABL_NO_LOAD
             load_chunk(nx2);
-#endif
             __builtin_amdgcn_sched_barrier(0);
         };
         Frag fa, fb;
@@ -727,7 +684,7 @@ __global__ __launch_bounds__(512, 2) void shared_conv_f16w_kernel(Conv16Args a) 
 }
 
 // ---- the input cut once for all heads (maps in bulk, several class heads) ----------------------------------------------------------
-// Ablation builds of the kernel above (W2_ABL_*, 8 frame pairs, one head): 0.89 ms with everything, 0.67 ms without its staging (loads,
+// Ablation builds of the kernel above (removed after commit 96899a8; 8 frame pairs, one head): 0.89 ms with everything, 0.67 ms without its staging (loads,
 // cut, LDS stores: the vector work that competes with the SIMD partner's matrix instructions), and the seven class heads of
 // tools/nusc_shasta/eval.py:86-101 each cut the SAME input tile again.  Here a bandwidth-bound pre-pass (conv16_precut_kernel) cuts every
 // map once into the fp16 piece image of ALL its tiles - [chunk][piece][octet][padded pixel slot][8 fp16], slots numbered as in the image
@@ -1105,7 +1062,6 @@ static int conv_multi(const float* x, const float* x_prev, int B, int in_channel
     a.H = H;
     a.W = W;
     a.heads = heads;
-#ifndef C16_NO_PRECUT
     // several heads over many maps and a workspace that holds the piece image: the input is cut once for all of them
     if (conv16p_serves(H, W, nmaps, heads) &&
         workspace_bytes >= shasta_shared_conv_multi_workspace_bytes(B) + conv16p_image_bytes(in_channels, H, W, nmaps) &&
@@ -1125,8 +1081,6 @@ static int conv_multi(const float* x, const float* x_prev, int B, int in_channel
         return check_launch("shared_conv_f16p");
     }
     (void)hipGetLastError();
-#endif
-#ifndef C16_NO_WIDE
     if (conv16w_serves(H, W, nmaps, heads)) {
         a.tiles_per_map = cdiv(H * W, W2_TILE);
         a.ntiles = a.tiles_per_map * nmaps;
@@ -1137,14 +1091,10 @@ static int conv_multi(const float* x, const float* x_prev, int B, int in_channel
         }
         (void)hipGetLastError();  // a device that grants less LDS: the 256-pixel form below
     }
-#endif
     a.tiles_per_map = cdiv(H * W, C16_TILE);
     a.ntiles = a.tiles_per_map * nmaps;
     a.tiles_per_xcd = cdiv(a.ntiles, 8);
-#ifndef C16_PB
-#define C16_PB 1
-#endif
-    (void)hipFuncSetAttribute((const void*)shared_conv_f16_kernel<C16_PB>, hipFuncAttributeMaxDynamicSharedMemorySize, C16_LDS);
-    hipLaunchKernelGGL(shared_conv_f16_kernel<C16_PB>, dim3(8 * a.tiles_per_xcd * heads), dim3(512 / C16_PB), C16_LDS, st, a);
+    (void)hipFuncSetAttribute((const void*)shared_conv_f16_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, C16_LDS);
+    hipLaunchKernelGGL(shared_conv_f16_kernel<1>, dim3(8 * a.tiles_per_xcd * heads), dim3(512), C16_LDS, st, a);
     return check_launch("shared_conv_f16");
 }

@@ -763,7 +763,6 @@ __global__ __launch_bounds__(GB_THREADS) void bev_gather_bwd_sorted_kernel(Gathe
         while (npad < m) npad <<= 1;
         for (int i = m + tid; i < npad; i += GB_THREADS) gb_keys[i] = 0xffffffffu;
         __syncthreads();
-#ifndef SHASTA_GB_SKIP_SORT  // timing diagnostic only (tools/time_gather_bwd.py): wrong results without the sort
         gb_wave_steps(gb_keys, npad, 2, 128, wave, lane);
         __syncthreads();
         for (int k = 256; k <= npad; k <<= 1) {
@@ -781,10 +780,8 @@ __global__ __launch_bounds__(GB_THREADS) void bev_gather_bwd_sorted_kernel(Gathe
             gb_wave_steps(gb_keys, npad, k, k, wave, lane);
             __syncthreads();
         }
-#endif
         // runs -> pixels.  A quarter wavefront (16 lanes x 4 channels) per run, so that a wavefront has four runs' loads in flight;
         // quarter qw walks the sorted positions [m qw / 64, m (qw + 1) / 64) and takes the runs that START there.
-#ifndef SHASTA_GB_SKIP_RUNS  // timing diagnostic only
         {
             const int qw = tid >> 4, ql = tid & 15;
             const int r1 = (int)((long)m * (qw + 1) / 64);
@@ -827,7 +824,6 @@ __global__ __launch_bounds__(GB_THREADS) void bev_gather_bwd_sorted_kernel(Gathe
                 }
             }
         }
-#endif
         __syncthreads();  // the next chunk reuses the LDS arrays - and may add to the same pixels: its reads come behind these stores
                           // (__syncthreads = release fence, barrier, acquire fence at workgroup scope; the wavefronts share the CU's L1)
     }

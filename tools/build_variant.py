@@ -1,7 +1,7 @@
 """Build a variant of the library for A/B runs: one source recompiled with extra -D flags, linked with the objects of the
 normal build.  usage: python tools/build_variant.py <name> <source.hip> [-DFLAG ...]  ->  tools/probes/_bin/libshasta_<name>.so
-(load it with SHASTA_HIP_LIB=<path>, see tools/gpu_ab.sh).  --export-all links without the export map (diagnostic builds that add an
-extern "C" accessor of their own, e.g. -DPAIR_STAMP)."""
+(load it with SHASTA_HIP_LIB=<path>, see tools/gpu_ab.sh).  --export-all links without the export map (variants that add an
+extern "C" accessor of their own)."""
 import os
 import subprocess
 import sys

@@ -1,7 +1,7 @@
 // aff_frame_kernel (aff_pieces.hip: six aff layers + both softmaxes in one pass, sibling workgroups exchange column partials) against
 // the two-kernel form's logits: the logits of aff_pieces_kernel are downloaded and both softmaxes are recomputed on the host in double.
 // Two residual buffers alternate between launches, so a sibling that read the previous launch's partials would be seen.
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -mllvm -amdgpu-mfma-vgpr-form=1 [-DSHASTA_AFF_STAMP] [-DAP_SHAPE_64] \
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -mllvm -amdgpu-mfma-vgpr-form=1 \
 //         -Ishasta_amd/csrc -Iinclude tools/probes/aff_frame_probe.hip -o /tmp/affframe && /tmp/affframe [frame-pairs] [N] [checked frames]
 #include "aff_pieces.hip"
 #include "aff_f16.hip"
@@ -153,18 +153,5 @@ int main(int argc, char** argv) {
     if (hipDeviceSynchronize() != hipSuccess) return 2;
     hipEventElapsedTime(&ms, e0, e1);
     printf("B=%d N=%d  aff_frame%s (everything) %.3f ms  [%s]\n", B, N, f16 ? "16" : "", ms / reps, bad ? "MISMATCH" : "ok");
-#ifdef SHASTA_AFF_STAMP
-    static unsigned long long h[4096][8];
-    hipMemcpyFromSymbol(h, HIP_SYMBOL(shasta::g_aff_stamp), sizeof(h));
-    const char* names[7] = {"layer 1 (load + cut + mfma)", "layers 2-5", "layer 6 mfma", "bias + statistics + publish", "staging + wait + combine", "write-out", "-"};
-    const int nwg = std::min(4096, B * ((T + 63) / 64));
-    for (int ph = 0; ph < 6; ++ph) {
-        std::vector<double> v;
-        for (int i = 0; i < nwg; ++i)
-            if (h[i][ph + 1] > h[i][ph]) v.push_back((double)(h[i][ph + 1] - h[i][ph]));
-        std::sort(v.begin(), v.end());
-        if (!v.empty()) printf("%-30s s_memtime ticks (100 MHz): p10 %.0f median %.0f p90 %.0f\n", names[ph], v[v.size() / 10], v[v.size() / 2], v[v.size() * 9 / 10]);
-    }
-#endif
     return bad;
 }
