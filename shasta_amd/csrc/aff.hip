@@ -58,7 +58,6 @@ __global__ __launch_bounds__(1024) void softmax_cols_kernel(const float* __restr
 // The same with TWO columns per lane (N even, ld even): a wave reads 128 consecutive columns of a row = 512 contiguous bytes per
 // instruction instead of 256 (8-byte loads and stores).  Identical arithmetic per column - max, exp, fixed-order sums over the same
 // 16 row groups - so the results are bit-identical to softmax_cols_kernel; 282 -> ... us at 512 frame-pairs (3.96 TB/s before).
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <int MAXR>
 __global__ __launch_bounds__(1024) void softmax_cols2_kernel(const float* __restrict__ matched, float* __restrict__ m2, int N, int T, int ld) {
     __shared__ f32x2 red[64][17];

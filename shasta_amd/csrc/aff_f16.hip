@@ -19,17 +19,10 @@
 #include <type_traits>
 
 #include "aff_frame.hpp"
-
-// the LDS-DMA asm below names m0 in its clobber list on purpose (it writes it)
-#pragma clang diagnostic ignored "-Winline-asm"
+#include "lds_dma.hpp"
+#include "pieces.hpp"
 
 namespace shasta {
-
-typedef _Float16 qh16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 qh16x2 __attribute__((ext_vector_type(2)));
-
-#define AQ_MFMA(a, b, c) \
-    __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(qh16x8, (a)), __builtin_bit_cast(qh16x8, (b)), (c), 0, 0, 0)
 
 constexpr int aq_max(int a, int b) { return a > b ? a : b; }
 
@@ -51,27 +44,10 @@ struct AqShape {
     static_assert(PER * (NS - 2) <= 63, "vmcnt is 6 bits");
 };
 
-// {a, b} -> packed fp16 pair, round to nearest even (v_cvt_pk_f16_f32)
-__device__ __forceinline__ uint32_t aq_cvt2(float a, float b) {
-    const qh16x2 v = {(_Float16)a, (_Float16)b};
-    return __builtin_bit_cast(uint32_t, v);
-}
-// x - h (exact in fp32) with h = the low / high half of a packed fp16 pair read as an f16 operand.  The results feed aq_cvt2 (a
-// compiler-generated VALU instruction), never an MFMA directly (pair_f16.hip, hazard rule)
-__device__ __forceinline__ float aq_res_lo(float x, uint32_t hpk) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(r) : "v"(x), "v"(hpk));
-    return r;
-}
-__device__ __forceinline__ float aq_res_hi(float x, uint32_t hpk) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r) : "v"(x), "v"(hpk));
-    return r;
-}
-// two scaled values -> their high and low piece pairs
+// two scaled values -> their high and low piece pairs (the residuals feed cvt_f16x2, never an MFMA directly: hazard rule of pieces.hpp)
 __device__ __forceinline__ void aq_cut2(float sa, float sb, uint32_t& h, uint32_t& l) {
-    h = aq_cvt2(sa, sb);
-    l = aq_cvt2(aq_res_lo(sa, h), aq_res_hi(sb, h));
+    h = cvt_f16x2(sa, sb);
+    l = cvt_f16x2(f16_res_lo(sa, h), f16_res_hi(sb, h));
 }
 
 // ---- pack: [layer][feature block][k step][piece 2][64 lanes] x 16 B, then one descale factor per output feature and layer ----------
@@ -108,7 +84,7 @@ __global__ __launch_bounds__(256) void aff_f16_pack_kernel(AffPack16Args a) {
         const int nks = ap_ksteps(layer, D), nfb = ap_fblocks(layer, D), kin = ap_kin(layer, D), nout = ap_out(layer, D);
         const float* W = a.aff[layer].weight;
         const float* dsc = a.out + ap16_scale_offset(layer, D);
-        qu32x4* o = reinterpret_cast<qu32x4*>(a.out) + ap16_frag_offset(layer, D) * 64;
+        u32x4* o = reinterpret_cast<u32x4*>(a.out) + ap16_frag_offset(layer, D) * 64;
         for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < nfb * nks * 64; e += gridDim.x * blockDim.x) {
             const int lane = e & 63, ks = (e >> 6) % nks, fb = (e >> 6) / nks;
             const int f = fb * 32 + (lane & 31), k0 = ks * 16 + (lane >> 5) * 8;
@@ -119,18 +95,18 @@ __global__ __launch_bounds__(256) void aff_f16_pack_kernel(AffPack16Args a) {
                 float w[2];
 #pragma unroll
                 for (int i = 0; i < 2; ++i) w[i] = (f < nout && k0 + 2 * j + i < kin) ? W[(size_t)f * kin + k0 + 2 * j + i] * s : 0.0f;
-                h[j] = aq_cvt2(w[0], w[1]);
-                const qh16x2 hv = __builtin_bit_cast(qh16x2, h[j]);
-                l[j] = aq_cvt2(w[0] - (float)hv[0], w[1] - (float)hv[1]);
+                h[j] = cvt_f16x2(w[0], w[1]);
+                const f16x2 hv = __builtin_bit_cast(f16x2, h[j]);
+                l[j] = cvt_f16x2(w[0] - (float)hv[0], w[1] - (float)hv[1]);
             }
-            qu32x4* dst = o + ((size_t)(fb * nks + ks) * 2) * 64 + lane;
-            dst[0] = qu32x4{h[0], h[1], h[2], h[3]};
-            dst[64] = qu32x4{l[0], l[1], l[2], l[3]};
+            u32x4* dst = o + ((size_t)(fb * nks + ks) * 2) * 64 + lane;
+            dst[0] = u32x4{h[0], h[1], h[2], h[3]};
+            dst[64] = u32x4{l[0], l[1], l[2], l[3]};
         }
     }
     // two spare (zero) fragments behind layer 6
-    qu32x4* spare = reinterpret_cast<qu32x4*>(a.out) + ap16_frag_offset(6, D) * 64;
-    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < 128; e += gridDim.x * blockDim.x) spare[e] = qu32x4{0, 0, 0, 0};
+    u32x4* spare = reinterpret_cast<u32x4*>(a.out) + ap16_frag_offset(6, D) * 64;
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < 128; e += gridDim.x * blockDim.x) spare[e] = u32x4{0, 0, 0, 0};
 }
 
 int aff_f16_pack(const shasta_weights* w, float* out, hipStream_t st) {
@@ -149,8 +125,8 @@ int aff_f16_pack(const shasta_weights* w, float* out, hipStream_t st) {
 
 // ---- layers ------------------------------------------------------------------------------------------------------------------------
 template <int KS>
-__device__ __forceinline__ void aq_load_w(const qu32x4* wl, int fb, int lane, qu32x4 (&w)[KS][2]) {
-    const qu32x4* frag = wl + (size_t)fb * KS * 2 * 64 + lane;
+__device__ __forceinline__ void aq_load_w(const u32x4* wl, int fb, int lane, u32x4 (&w)[KS][2]) {
+    const u32x4* frag = wl + (size_t)fb * KS * 2 * 64 + lane;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
         w[ks][0] = frag[(ks * 2) * 64];
@@ -160,24 +136,23 @@ __device__ __forceinline__ void aq_load_w(const qu32x4* wl, int fb, int lane, qu
 
 // activation pieces of k step ks, row block rb, from a hidden piece image (ROW bytes per row, IMG bytes per piece)
 template <int ROW, int IMG>
-__device__ __forceinline__ void aq_load_h(const char* H, int rb, int ks, int lane, qu32x4 (&x)[2]) {
+__device__ __forceinline__ void aq_load_h(const char* H, int rb, int ks, int lane, u32x4 (&x)[2]) {
     const char* p = H + (rb * 32 + (lane & 31)) * ROW + (ks * 16 + (lane >> 5) * 8) * 2;
-    x[0] = *reinterpret_cast<const qu32x4*>(p);
-    x[1] = *reinterpret_cast<const qu32x4*>(p + IMG);
+    x[0] = *reinterpret_cast<const u32x4*>(p);
+    x[1] = *reinterpret_cast<const u32x4*>(p + IMG);
 }
 
-// the three piece products of one k step, small to large (first operand = weight pieces, second = activation pieces; [0] = high)
-__device__ __forceinline__ void aq_step(const qu32x4 (&w)[2], const qu32x4 (&x)[2], f32x16& acc) {
-    acc = AQ_MFMA(w[1], x[0], acc);
-    acc = AQ_MFMA(w[0], x[1], acc);
-    acc = AQ_MFMA(w[0], x[0], acc);
+// the three piece products of one k step (first operand = weight pieces, second = activation pieces; [0] = high)
+__device__ __forceinline__ void aq_step(const u32x4 (&w)[2], const u32x4 (&x)[2], f32x16& acc) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) acc = mfma_32x32x16_f16(w[kProductsF16[q].a], x[kProductsF16[q].b], acc);
 }
 
 template <int KS, int ROW, int IMG>
-__device__ __forceinline__ void aq_hidden(const qu32x4 (&w)[KS][2], int rb, const char* Hin, int lane, f32x16& acc) {
+__device__ __forceinline__ void aq_hidden(const u32x4 (&w)[KS][2], int rb, const char* Hin, int lane, f32x16& acc) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-        qu32x4 x[2];
+        u32x4 x[2];
         aq_load_h<ROW, IMG>(Hin, rb, ks, lane, x);
         aq_step(w[ks], x, acc);
     }
@@ -225,8 +200,8 @@ __device__ __forceinline__ void aq_finish(f32x16 (&h)[NT], const int (&fbs)[NT],
                 aq_cut2(h[t][4 * g] * s, h[t][4 * g + 1] * s, h0, l0);
                 aq_cut2(h[t][4 * g + 2] * s, h[t][4 * g + 3] * s, h1, l1);
                 char* dst = row + (fbs[t] * 32 + 8 * g + 4 * hh) * 2;
-                *reinterpret_cast<qu32x2*>(dst) = qu32x2{h0, h1};
-                *reinterpret_cast<qu32x2*>(dst + IMG) = qu32x2{l0, l1};
+                *reinterpret_cast<u32x2*>(dst) = u32x2{h0, h1};
+                *reinterpret_cast<u32x2*>(dst + IMG) = u32x2{l0, l1};
             }
     }
     __syncthreads();
@@ -246,7 +221,7 @@ __device__ __forceinline__ void aq_mlp(const AffPiecesArgs& a, char* smem, int g
     float* rsc0 = pm + WAVES * 32;                          // [ROWS] row factors, two generations
     float* rsc1 = rsc0 + ROWS;
     const int D = a.D;
-    const qu32x4* wq = reinterpret_cast<const qu32x4*>(a.wp);
+    const u32x4* wq = reinterpret_cast<const u32x4*>(a.wp);
     const float* sec = reinterpret_cast<const float*>(a.wp);
     const f32x16 zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const int n = lane & 31, hh = lane >> 5, rbw = wid >> 1;
@@ -277,21 +252,21 @@ __device__ __forceinline__ void aq_mlp(const AffPiecesArgs& a, char* smem, int g
                 const char* base = xbase + (size_t)c * 128;
                 const uint32_t dst = sl + (uint32_t)((16 * wid + 8 * jj) * 128);
                 const uint32_t vo = c == NC - 1 ? xoff_last[jj] : xoff[jj];
-                asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 nt" ::"v"(vo), "s"(base), "s"(dst) : "memory", "m0");
+                lds_dma_x4_nt(vo, base, dst);
             }
 #pragma unroll
             for (int jj = 0; jj < WPW; ++jj) {
                 const int fi = WPW * wid + jj, fb = fi >> 2, within = fi & 3;  // within = 2 (k step) + piece
                 const char* base = wbase + ((size_t)(fb * nks + 2 * c) * 2 + within) * 1024;
                 const uint32_t dst = sl + (uint32_t)(S::L1X + fi * 1024);
-                asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(woff), "s"(base), "s"(dst) : "memory", "m0");
+                lds_dma_x4(woff, base, dst);
             }
         };
         const int xrow = rbw * 32 + n, xsw = (xrow >> 1) & 7, hh2 = hh * 2;
         // the lane's 2 x 8 values of chunk c -> fp16 pieces under the chunk's row scale; sinv undoes it
         // (tail: the chunk that holds column D - and behind it the padding of the residual rows and a phantom k step - is cut with those
         // positions zeroed: their weights are zero, but what the caller's padding columns hold need not be finite)
-        auto prep = [&](auto tail, int c, int slot, qu32x4 (&xh)[2], qu32x4 (&xl)[2], float& sinv) {
+        auto prep = [&](auto tail, int c, int slot, u32x4 (&xh)[2], u32x4 (&xl)[2], float& sinv) {
             const char* sl = smem + slot * S::L1SLOT;
             float v[2][8];
             float m = 0.0f;
@@ -323,19 +298,19 @@ __device__ __forceinline__ void aq_mlp(const AffPiecesArgs& a, char* smem, int g
                     xl[st][j] = pl;
                 }
         };
-        auto mma = [&](int slot, const qu32x4 (&xh)[2], const qu32x4 (&xl)[2], float sinv) {
-            const qu32x4* wf = reinterpret_cast<const qu32x4*>(smem + slot * S::L1SLOT + S::L1X) + lane;
+        auto mma = [&](int slot, const u32x4 (&xh)[2], const u32x4 (&xl)[2], float sinv) {
+            const u32x4* wf = reinterpret_cast<const u32x4*>(smem + slot * S::L1SLOT + S::L1X) + lane;
             f32x16 t0 = zero16, t1 = zero16;
 #pragma unroll
             for (int st = 0; st < 2; ++st) {
-                const qu32x4 w0h = wf[((fb0 * 2 + st) * 2) * 64], w0l = wf[((fb0 * 2 + st) * 2 + 1) * 64];
-                const qu32x4 w1h = wf[(((fb0 + 1) * 2 + st) * 2) * 64], w1l = wf[(((fb0 + 1) * 2 + st) * 2 + 1) * 64];
-                t0 = AQ_MFMA(w0l, xh[st], t0);
-                t1 = AQ_MFMA(w1l, xh[st], t1);
-                t0 = AQ_MFMA(w0h, xl[st], t0);
-                t1 = AQ_MFMA(w1h, xl[st], t1);
-                t0 = AQ_MFMA(w0h, xh[st], t0);
-                t1 = AQ_MFMA(w1h, xh[st], t1);
+                const u32x4 w0h = wf[((fb0 * 2 + st) * 2) * 64], w0l = wf[((fb0 * 2 + st) * 2 + 1) * 64];
+                const u32x4 w1h = wf[(((fb0 + 1) * 2 + st) * 2) * 64], w1l = wf[(((fb0 + 1) * 2 + st) * 2 + 1) * 64];
+                t0 = mfma_32x32x16_f16(w0l, xh[st], t0);
+                t1 = mfma_32x32x16_f16(w1l, xh[st], t1);
+                t0 = mfma_32x32x16_f16(w0h, xl[st], t0);
+                t1 = mfma_32x32x16_f16(w1h, xl[st], t1);
+                t0 = mfma_32x32x16_f16(w0h, xh[st], t0);
+                t1 = mfma_32x32x16_f16(w1h, xh[st], t1);
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -347,10 +322,10 @@ __device__ __forceinline__ void aq_mlp(const AffPiecesArgs& a, char* smem, int g
         for (int c = 0; c < NS - 1; ++c)
             if (c < NC) issue(c, c);
         // chunk 0 has landed when at most the NS - 2 younger chunks are outstanding
-        if (NC >= NS - 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER * (NS - 2)) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (NC >= NS - 1) wait_vmcnt<PER * (NS - 2)>();
+        else wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
-        qu32x4 xh[2], xl[2];
+        u32x4 xh[2], xl[2];
         float sinv;
         if (NC == 1) prep(std::true_type{}, 0, 0, xh, xl, sinv);
         else prep(std::false_type{}, 0, 0, xh, xl, sinv);
@@ -359,12 +334,12 @@ __device__ __forceinline__ void aq_mlp(const AffPiecesArgs& a, char* smem, int g
         for (int c = 0; c < NC; ++c) {
             // chunk c + 1 must have landed (requested so far: up to chunk c + NS - 2); the barrier also certifies that chunk c - 1
             // has been consumed, whose slot is refilled with chunk c + NS - 1
-            if (NS > 3 && c + NS - 2 <= NC - 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER * (NS > 3 ? NS - 3 : 0)) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (NS > 3 && c + NS - 2 <= NC - 1) wait_vmcnt<PER * (NS > 3 ? NS - 3 : 0)>();
+            else wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();
             if (c + NS - 1 < NC) issue(c + NS - 1, slot == 0 ? NS - 1 : slot - 1);
             const int nslot = slot == NS - 1 ? 0 : slot + 1;
-            qu32x4 yh[2], yl[2];
+            u32x4 yh[2], yl[2];
             float tinv;
             const bool more = c + 1 < NC;  // the last trip cuts its own chunk again (unused): one straight-line body per case
             if (c + 1 >= NC - 1) {
@@ -380,13 +355,13 @@ __device__ __forceinline__ void aq_mlp(const AffPiecesArgs& a, char* smem, int g
             slot = nslot;
         }
     }
-    const qu32x4* w2 = wq + ap16_frag_offset(1, D) * 64;
-    const qu32x4* w3 = wq + ap16_frag_offset(2, D) * 64;
-    const qu32x4* w4 = wq + ap16_frag_offset(3, D) * 64;
-    const qu32x4* w5 = wq + ap16_frag_offset(4, D) * 64;
-    const qu32x4* w6 = wq + ap16_frag_offset(5, D) * 64;
+    const u32x4* w2 = wq + ap16_frag_offset(1, D) * 64;
+    const u32x4* w3 = wq + ap16_frag_offset(2, D) * 64;
+    const u32x4* w4 = wq + ap16_frag_offset(3, D) * 64;
+    const u32x4* w5 = wq + ap16_frag_offset(4, D) * 64;
+    const u32x4* w6 = wq + ap16_frag_offset(5, D) * 64;
     {  // layer-1 output: 2 tiles per wave, the partner wave holds the row's other 64 features; -> image A (over the ring)
-        qu32x4 wn[8][2];
+        u32x4 wn[8][2];
         aq_load_w<8>(w2, wid & 1, lane, wn);  // next layer's weights: in flight across the barriers
         const int fb0 = 2 * (wid & 1);
         f32x16 h[2] = {out0, out1};
@@ -397,7 +372,7 @@ __device__ __forceinline__ void aq_mlp(const AffPiecesArgs& a, char* smem, int g
         // 128 -> 64: 2 feature blocks x RB row blocks = one task per wave; A -> B
         f32x16 t[1] = {zero16};
         aq_hidden<8, AP_AROW, AIMG>(wn, rbw, HA, lane, t[0]);
-        qu32x4 w3n[4][2];
+        u32x4 w3n[4][2];
         if (wid < RB) aq_load_w<4>(w3, 0, lane, w3n);
         aq_activate(t[0], wid & 1, hh, rsc0[rbw * 32 + n], sec + ap16_scale_offset(1, D), a.bias[1]);
         const int f1[1] = {wid & 1};
@@ -409,14 +384,14 @@ __device__ __forceinline__ void aq_mlp(const AffPiecesArgs& a, char* smem, int g
             aq_hidden<4, AP_BROW, BIMG>(w3n, wid, HB, lane, t[0]);
             aq_activate(t[0], 0, hh, rsc1[wid * 32 + n], sec + ap16_scale_offset(2, D), a.bias[2]);
         }
-        qu32x4 w4n[2][2];
+        u32x4 w4n[2][2];
         aq_load_w<2>(w4, wid & 1, lane, w4n);
         const int f0[1] = {0};
         aq_finish<1, AP_AROW, AIMG>(t, f0, act3 ? wid : 0, act3, false, HA, pm, rsc0, lane, wid);
         // 32 -> 64: 2 x RB tasks; A -> B
         t[0] = zero16;
         aq_hidden<2, AP_AROW, AIMG>(w4n, rbw, HA, lane, t[0]);
-        qu32x4 w5n[2][4][2];
+        u32x4 w5n[2][4][2];
         aq_load_w<4>(w5, 2 * (wid & 1), lane, w5n[0]);
         aq_load_w<4>(w5, 2 * (wid & 1) + 1, lane, w5n[1]);
         aq_activate(t[0], wid & 1, hh, rsc0[rbw * 32 + n], sec + ap16_scale_offset(3, D), a.bias[3]);
@@ -437,13 +412,13 @@ __device__ __forceinline__ void aq_mlp(const AffPiecesArgs& a, char* smem, int g
     for (int i = 0; i < NFW; ++i)
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) acc[i][rb] = zero16;
-    qu32x4 wc[NFW][2];
-    auto load6 = [&](int ks, qu32x4 (&w)[NFW][2]) {
+    u32x4 wc[NFW][2];
+    auto load6 = [&](int ks, u32x4 (&w)[NFW][2]) {
 #pragma unroll
         for (int i = 0; i < NFW; ++i) {
             const int fb = wid + WAVES * i;
             if (fb < nfb) {  // wave-uniform
-                const qu32x4* frag = w6 + ((size_t)fb * 8 + ks) * 2 * 64 + lane;
+                const u32x4* frag = w6 + ((size_t)fb * 8 + ks) * 2 * 64 + lane;
                 w[i][0] = frag[0];
                 w[i][1] = frag[64];
             }
@@ -452,9 +427,9 @@ __device__ __forceinline__ void aq_mlp(const AffPiecesArgs& a, char* smem, int g
     load6(0, wc);
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
-        qu32x4 wnx[NFW][2];
+        u32x4 wnx[NFW][2];
         if (ks + 1 < 8) load6(ks + 1, wnx);
-        qu32x4 x[RB][2];
+        u32x4 x[RB][2];
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) aq_load_h<AP_AROW, AIMG>(HA, rb, ks, lane, x[rb]);
 #pragma unroll

@@ -8,9 +8,6 @@
 
 namespace shasta {
 
-typedef uint32_t qu32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t qu32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int AP_AROW = 272;  // bytes per row of image A (128 bf16 + 16 B pad: 68 dwords, conflict-free b128 reads)
 constexpr int AP_BROW = 144;  // bytes per row of image B (64 bf16 + 16 B pad: 36 dwords, conflict-free)
 constexpr int AP_SCOLS = 256, AP_SROW = AP_SCOLS + 4;  // output staging: ROWS x 256 features per pass

@@ -1,9 +1,7 @@
 // K6 for large batches: the six aff layers (det3d/models/tracker/shasta.py:94-106, applied :323) and the row softmax (:324)
-// with every fp32 product formed from exact bf16 pieces on the bf16 matrix path - the arithmetic of anchor_split.hip /
-// gemm_pieces.hip:  a = a_hi + a_mid + a_lo (8 significand bits each, cut by truncation, exact),  w * a = the six piece products
-// of weight 2^0 .. 2^-16 accumulated in the fp32 accumulator of v_mfma_f32_32x32x16_bf16.  Six bf16 MFMAs of K = 16 replace
-// 32 f32 MFMAs of 16x16x4: 2.7 x fewer matrix cycles per fp32 product than aff_fused_kernel (aff.hip), which stays the kernel
-// of small batches and of tables wider than 512 columns.
+// with every fp32 product formed from exact bf16 pieces on the bf16 matrix path (the six piece products of pieces.hpp).  Six bf16
+// MFMAs of K = 16 replace 32 f32 MFMAs of 16x16x4: 2.7 x fewer matrix cycles per fp32 product than aff_fused_kernel (aff.hip), which
+// stays the kernel of small batches and of tables wider than 512 columns.
 //
 // Orientation: out^T[feature][row] = W[feature][k] . h^T[k][row].  First MFMA operand = a 32-feature block of W, second =
 // the 32 residual rows of the workgroup; a lane's 16 result registers are features (r&3) + 8 (r>>2) + 4 (lane>>5) of row
@@ -26,23 +24,10 @@
 //  and the cuts 15 k do not overlap: one barrier per chunk keeps the two waves of a SIMD in step), layers 2-5 31 k (latency of
 //  their weight loads and four barriers), layer 6 30 k (MFMA-bound), softmax statistics 30 k, output 61 k (20 k without the stores).
 #include "aff_frame.hpp"
-
-// the LDS-DMA asm below names m0 in its clobber list on purpose (it writes it)
-#pragma clang diagnostic ignored "-Winline-asm"
+#include "lds_dma.hpp"
+#include "pieces.hpp"
 
 namespace shasta {
-
-typedef __bf16 qbf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void ap_cut3(float a, float& h, float& m, float& l) {
-    h = __uint_as_float(__float_as_uint(a) & 0xffff0000u);
-    const float r = a - h;
-    m = __uint_as_float(__float_as_uint(r) & 0xffff0000u);
-    l = r - m;
-}
-__device__ __forceinline__ uint32_t ap_top2(float even, float odd) {
-    return __builtin_amdgcn_perm(__float_as_uint(odd), __float_as_uint(even), 0x07060302u);
-}
 
 struct AffPackArgs {
     shasta_linear aff[6];
@@ -64,12 +49,12 @@ __global__ __launch_bounds__(256) void aff_pieces_pack_kernel(AffPackArgs a) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const float w = (f < nout && k0 + j < kin) ? W[(size_t)f * kin + k0 + j] : 0.0f;
-                ap_cut3(w, h[j], m[j], l[j]);
+                cut3_bf16(w, h[j], m[j], l[j]);
             }
-            qu32x4* dst = reinterpret_cast<qu32x4*>(o) + ((size_t)(fb * nks + ks) * 3) * 64 + lane;
-            dst[0] = qu32x4{ap_top2(h[0], h[1]), ap_top2(h[2], h[3]), ap_top2(h[4], h[5]), ap_top2(h[6], h[7])};
-            dst[64] = qu32x4{ap_top2(m[0], m[1]), ap_top2(m[2], m[3]), ap_top2(m[4], m[5]), ap_top2(m[6], m[7])};
-            dst[128] = qu32x4{ap_top2(l[0], l[1]), ap_top2(l[2], l[3]), ap_top2(l[4], l[5]), ap_top2(l[6], l[7])};
+            u32x4* dst = reinterpret_cast<u32x4*>(o) + ((size_t)(fb * nks + ks) * 3) * 64 + lane;
+            dst[0] = u32x4{pack_bf16x2(h[0], h[1]), pack_bf16x2(h[2], h[3]), pack_bf16x2(h[4], h[5]), pack_bf16x2(h[6], h[7])};
+            dst[64] = u32x4{pack_bf16x2(m[0], m[1]), pack_bf16x2(m[2], m[3]), pack_bf16x2(m[4], m[5]), pack_bf16x2(m[6], m[7])};
+            dst[128] = u32x4{pack_bf16x2(l[0], l[1]), pack_bf16x2(l[2], l[3]), pack_bf16x2(l[4], l[5]), pack_bf16x2(l[6], l[7])};
         }
     }
 }
@@ -83,20 +68,13 @@ int aff_pieces_pack(const shasta_weights* w, float* out, hipStream_t st) {
     return check_launch("aff_pieces_pack");
 }
 
-#define AP_MFMA(a, b, c) \
-    __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(qbf16x8, (a)), __builtin_bit_cast(qbf16x8, (b)), (c), 0, 0, 0)
-
-// the six piece products of one k step, small to large (first operand = weight pieces, second = activation pieces)
-__device__ __forceinline__ void ap_step(const qu32x4 (&w)[3], const qu32x4 (&x)[3], f32x16& acc) {
-    acc = AP_MFMA(w[2], x[0], acc);
-    acc = AP_MFMA(w[0], x[2], acc);
-    acc = AP_MFMA(w[1], x[1], acc);
-    acc = AP_MFMA(w[1], x[0], acc);
-    acc = AP_MFMA(w[0], x[1], acc);
-    acc = AP_MFMA(w[0], x[0], acc);
+// the six piece products of one k step (first operand = weight pieces, second = activation pieces)
+__device__ __forceinline__ void ap_step(const u32x4 (&w)[3], const u32x4 (&x)[3], f32x16& acc) {
+#pragma unroll
+    for (int q = 0; q < 6; ++q) acc = mfma_32x32x16_bf16(w[kProductsBf16[q].a], x[kProductsBf16[q].b], acc);
 }
 
-__device__ __forceinline__ void ap_load_w(const qu32x4* frag, int lane, qu32x4 (&w)[3]) {
+__device__ __forceinline__ void ap_load_w(const u32x4* frag, int lane, u32x4 (&w)[3]) {
     w[0] = frag[lane];
     w[1] = frag[64 + lane];
     w[2] = frag[128 + lane];
@@ -104,11 +82,11 @@ __device__ __forceinline__ void ap_load_w(const qu32x4* frag, int lane, qu32x4 (
 
 // activation fragment of k step `ks`, row block rb, from a hidden piece image (ROW bytes per row, IMG bytes per piece)
 template <int ROW, int IMG>
-__device__ __forceinline__ void ap_load_h(const char* H, int rb, int ks, int lane, qu32x4 (&x)[3]) {
+__device__ __forceinline__ void ap_load_h(const char* H, int rb, int ks, int lane, u32x4 (&x)[3]) {
     const char* p = H + (rb * 32 + (lane & 31)) * ROW + (ks * 16 + (lane >> 5) * 8) * 2;
-    x[0] = *reinterpret_cast<const qu32x4*>(p);
-    x[1] = *reinterpret_cast<const qu32x4*>(p + IMG);
-    x[2] = *reinterpret_cast<const qu32x4*>(p + 2 * IMG);
+    x[0] = *reinterpret_cast<const u32x4*>(p);
+    x[1] = *reinterpret_cast<const u32x4*>(p + IMG);
+    x[2] = *reinterpret_cast<const u32x4*>(p + 2 * IMG);
 }
 
 // acc (+ bias, ReLU) of (feature block fb, row block rb) -> the piece image of the next layer
@@ -121,24 +99,24 @@ __device__ __forceinline__ void ap_store_h(char* H, int fb, int rb, int lane, co
         const float b[4] = {bias[f0], bias[f0 + 1], bias[f0 + 2], bias[f0 + 3]};
         float h[4], m[4], l[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) ap_cut3(relu_nan(acc[4 * g + j] + b[j]), h[j], m[j], l[j]);
+        for (int j = 0; j < 4; ++j) cut3_bf16(relu_nan(acc[4 * g + j] + b[j]), h[j], m[j], l[j]);
         char* dst = H + n * ROW + f0 * 2;
-        *reinterpret_cast<qu32x2*>(dst) = qu32x2{ap_top2(h[0], h[1]), ap_top2(h[2], h[3])};
-        *reinterpret_cast<qu32x2*>(dst + IMG) = qu32x2{ap_top2(m[0], m[1]), ap_top2(m[2], m[3])};
-        *reinterpret_cast<qu32x2*>(dst + 2 * IMG) = qu32x2{ap_top2(l[0], l[1]), ap_top2(l[2], l[3])};
+        *reinterpret_cast<u32x2*>(dst) = u32x2{pack_bf16x2(h[0], h[1]), pack_bf16x2(h[2], h[3])};
+        *reinterpret_cast<u32x2*>(dst + IMG) = u32x2{pack_bf16x2(m[0], m[1]), pack_bf16x2(m[2], m[3])};
+        *reinterpret_cast<u32x2*>(dst + 2 * IMG) = u32x2{pack_bf16x2(l[0], l[1]), pack_bf16x2(l[2], l[3])};
     }
 }
 
 // one (feature block, row block) task of a hidden layer with KS k steps: weights from global fragments, activations from LDS
 template <int KS, int ROW, int IMG>
-__device__ __forceinline__ void ap_hidden_task(const qu32x4* wl, int fb, int rb, const char* Hin, int lane, f32x16& acc) {
-    const qu32x4* frag = wl + (size_t)fb * KS * 3 * 64;
-    qu32x4 w[KS][3];
+__device__ __forceinline__ void ap_hidden_task(const u32x4* wl, int fb, int rb, const char* Hin, int lane, f32x16& acc) {
+    const u32x4* frag = wl + (size_t)fb * KS * 3 * 64;
+    u32x4 w[KS][3];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) ap_load_w(frag + ks * 3 * 64, lane, w[ks]);
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-        qu32x4 x[3];
+        u32x4 x[3];
         ap_load_h<ROW, IMG>(Hin, rb, ks, lane, x);
         ap_step(w[ks], x, acc);
     }
@@ -155,7 +133,7 @@ __device__ __forceinline__ void ap_mlp(const AffPiecesArgs& a, char* smem, int g
     char* HA = smem;              // [3][ROWS][272 B]: layer outputs of width 128 / 32
     char* HB = smem + S::ABYTES;  // [3][ROWS][144 B]: layer outputs of width 64
     const int D = a.D;
-    const qu32x4* wp = reinterpret_cast<const qu32x4*>(a.wp);
+    const u32x4* wp = reinterpret_cast<const u32x4*>(a.wp);
     const f32x16 zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
     // ---- layer 1 (K = D -> 128): wave = (row block wid >> 1, feature blocks 2 (wid & 1) + {0, 1}).  Residual rows and weight
@@ -190,14 +168,14 @@ __device__ __forceinline__ void ap_mlp(const AffPiecesArgs& a, char* smem, int g
                 const char* base = xbase + (size_t)c * 128;
                 const uint32_t dst = sl + (uint32_t)((16 * wid + 8 * jj) * 128);
                 const uint32_t vo = c == NC - 1 ? xoff_last[jj] : xoff[jj];
-                asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 nt" ::"v"(vo), "s"(base), "s"(dst) : "memory", "m0");
+                lds_dma_x4_nt(vo, base, dst);
             }
 #pragma unroll
             for (int jj = 0; jj < WPW; ++jj) {
                 const int f24 = WPW * wid + jj, fb = f24 / 6, within = f24 % 6;  // within = 3 (k step) + piece
                 const char* base = wbase + ((size_t)(fb * nks + 2 * c) * 3 + within) * 1024;
                 const uint32_t dst = sl + (uint32_t)(S::L1X + f24 * 1024);
-                asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(woff), "s"(base), "s"(dst) : "memory", "m0");
+                lds_dma_x4(woff, base, dst);
             }
         };
         f32x16 acc0 = zero16, acc1 = zero16;
@@ -215,20 +193,15 @@ __device__ __forceinline__ void ap_mlp(const AffPiecesArgs& a, char* smem, int g
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] = k0 + e < D ? v[e] : 0.0f;
                 }
-                qu32x4 w0[3], w1[3];
-                const qu32x4* wf = reinterpret_cast<const qu32x4*>(sl + S::L1X) + lane;
+                u32x4 w0[3], w1[3];
+                const u32x4* wf = reinterpret_cast<const u32x4*>(sl + S::L1X) + lane;
 #pragma unroll
                 for (int pc = 0; pc < 3; ++pc) {
                     w0[pc] = wf[(fb0 * 6 + st * 3 + pc) * 64];
                     w1[pc] = wf[((fb0 + 1) * 6 + st * 3 + pc) * 64];
                 }
-                float h[8], m[8], l[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) ap_cut3(v[e], h[e], m[e], l[e]);
-                qu32x4 x[3];
-                x[0] = qu32x4{ap_top2(h[0], h[1]), ap_top2(h[2], h[3]), ap_top2(h[4], h[5]), ap_top2(h[6], h[7])};
-                x[1] = qu32x4{ap_top2(m[0], m[1]), ap_top2(m[2], m[3]), ap_top2(m[4], m[5]), ap_top2(m[6], m[7])};
-                x[2] = qu32x4{ap_top2(l[0], l[1]), ap_top2(l[2], l[3]), ap_top2(l[4], l[5]), ap_top2(l[6], l[7])};
+                u32x4 x[3];
+                cut3_bf16x8(v, x);
                 // 256 idle cycles behind each group of six MFMAs.  Without them this phase (eight waves issuing MFMAs back to back
                 // next to the LDS-DMA) makes the chip fall into a lower clock state for the WHOLE step: measured on three boxes
                 // (tools/gpu_ab.sh, alternating): 12.00 - 12.06 ms per step and 1075 W without the pauses against 11.52 - 11.65 ms
@@ -246,8 +219,8 @@ __device__ __forceinline__ void ap_mlp(const AffPiecesArgs& a, char* smem, int g
 #pragma unroll 1
         for (int c = 0; c < NC; ++c) {
             // chunks issued after chunk c: min(NS - 2, NC - 1 - c)
-            if (NS > 2 && c + NS - 2 < NC) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER * (NS - 2)) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (NS > 2 && c + NS - 2 < NC) wait_vmcnt<PER * (NS - 2)>();
+            else wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();
             if (c + NS - 1 < NC) issue(c + NS - 1, slot == 0 ? NS - 1 : slot - 1);
             compute(c, slot);
@@ -258,11 +231,11 @@ __device__ __forceinline__ void ap_mlp(const AffPiecesArgs& a, char* smem, int g
         ap_store_h<AP_AROW, AIMG>(HA, fb0 + 1, rb, lane, acc1, a.bias[0]);
     }
     __syncthreads();
-    const qu32x4* w2 = wp + ap_layer_offset(1, D) * 64;
-    const qu32x4* w3 = wp + ap_layer_offset(2, D) * 64;
-    const qu32x4* w4 = wp + ap_layer_offset(3, D) * 64;
-    const qu32x4* w5 = wp + ap_layer_offset(4, D) * 64;
-    const qu32x4* w6 = wp + ap_layer_offset(5, D) * 64;
+    const u32x4* w2 = wp + ap_layer_offset(1, D) * 64;
+    const u32x4* w3 = wp + ap_layer_offset(2, D) * 64;
+    const u32x4* w4 = wp + ap_layer_offset(3, D) * 64;
+    const u32x4* w5 = wp + ap_layer_offset(4, D) * 64;
+    const u32x4* w6 = wp + ap_layer_offset(5, D) * 64;
     {  // 128 -> 64: 2 feature blocks x RB row blocks = one task per wave; A -> B
         f32x16 acc = zero16;
         ap_hidden_task<8, AP_AROW, AIMG>(w2, wid & 1, wid >> 1, HA, lane, acc);
@@ -300,14 +273,14 @@ __device__ __forceinline__ void ap_mlp(const AffPiecesArgs& a, char* smem, int g
         for (int rb = 0; rb < RB; ++rb) acc[i][rb] = zero16;
 #pragma unroll 1
     for (int ks = 0; ks < 8; ++ks) {
-        qu32x4 x[RB][3];
+        u32x4 x[RB][3];
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) ap_load_h<AP_AROW, AIMG>(HA, rb, ks, lane, x[rb]);
 #pragma unroll
         for (int i = 0; i < NFW; ++i) {
             const int fb = wid + WAVES * i;
             if (fb < nfb) {  // wave-uniform
-                qu32x4 w[3];
+                u32x4 w[3];
                 ap_load_w(w6 + ((size_t)fb * 8 + ks) * 3 * 64, lane, w);
 #pragma unroll
                 for (int rb = 0; rb < RB; ++rb) ap_step(w, x[rb], acc[i][rb]);

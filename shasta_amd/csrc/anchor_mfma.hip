@@ -20,9 +20,7 @@
 // (a clock-stamp build, removed after commit 96899a8) read 2200 cycles per tile at 64 rows = 93 % of the matrix pipe, at an in-kernel clock
 // of 1.98 GHz (32 rows: 1140 of 1024 cycles at 1.72 GHz - the chip lowers its clock under the combined HBM + MFMA load).  Split-K partials are reduced afterwards in a fixed order.
 #include "common.hpp"
-
-// the LDS-DMA asm below names m0 in its clobber list on purpose (it writes it)
-#pragma clang diagnostic ignored "-Winline-asm"
+#include "lds_dma.hpp"
 
 #include <type_traits>
 
@@ -37,11 +35,6 @@ struct AnchorMfmaArgs {
 
 // weights are read exactly once per launch: the weight stream is issued non-temporal (nt) so that the activation vectors
 // and the small weights of the following kernels stay resident in L2 / Infinity Cache (MI355X_MICROARCH.md, row nt-weights)
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // XT == 0: 16 batch rows per pass with 16x16x4 MFMA; XT == 1 / 2: 32 / 64 batch rows per pass with 32x32x2 MFMA
 // (XT accumulators share every weight fragment; at 64 rows the kernel is MFMA-bound, 2048 SIMD cycles per 4 KB tile).
@@ -99,9 +92,7 @@ __global__ __launch_bounds__(256) void anchor_l1_mfma_kernel(AnchorMfmaArgs a) {
     constexpr int DSLOTS = (ND + DPS - 1) / DPS;
     static_assert(DSLOTS + NR < NM, "the fragment reads must end a few MFMAs before the tile does");
     // The f32 MFMA does not overlap VALU work, so the loop must not contain any: the tile advance is added to the uniform
-    // base on the scalar unit and the per-lane 32-bit offset goes into the instruction's VGPR-offset field
-    // (global_load_lds_dwordx4 voff, s[base:base+1]).  hipcc only emits the 64-bit-VGPR-address form for the LDS-DMA
-    // builtin (two v_lshl_add_u64 per instruction: measured 2560 instead of 2048 cycles per tile at 64 rows), hence the asm.
+    // base on the scalar unit and the per-lane 32-bit offset goes into the instruction's VGPR-offset field (lds_dma_x4).
     const uint32_t wlds = (uint32_t)(size_t)((__attribute__((address_space(3))) float*)wring);
     const uint32_t xlds = (uint32_t)(size_t)((__attribute__((address_space(3))) float*)xring);
     auto dma = [&](int t, int idx) {  // instruction idx of tile t
@@ -109,13 +100,11 @@ __global__ __launch_bounds__(256) void anchor_l1_mfma_kernel(AnchorMfmaArgs a) {
         if (idx < 4) {
             const char* base = wub + ko;
             const uint32_t dst = wlds + (uint32_t)(((t % NS) * WSTRIDE + idx * 256) * 4);
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 nt" ::"v"(woff[idx]), "s"(base), "s"(dst)
-                         : "memory", "m0");
+            lds_dma_x4_nt(woff[idx], base, dst);
         } else {
             const char* base = xub + ko;
             const uint32_t dst = xlds + (uint32_t)(((t % NS) * XSTRIDE + (idx - 4) * 256) * 4);
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(xoff[idx - 4]), "s"(base), "s"(dst)
-                         : "memory", "m0");
+            lds_dma_x4(xoff[idx - 4], base, dst);
         }
     };
     auto issue = [&](int t) {
@@ -179,8 +168,8 @@ __global__ __launch_bounds__(256) void anchor_l1_mfma_kernel(AnchorMfmaArgs a) {
 #pragma unroll 1
     for (; issued < NS && issued < NT; ++issued) issue(issued);
     Frag fa, fb;
-    if (NT >= NS) wait_vm<PER_TILE*(NS - 1)>();
-    else wait_vm<0>();
+    if (NT >= NS) wait_vmcnt<PER_TILE*(NS - 1)>();
+    else wait_vmcnt<0>();
     if (NT > 0) read_frags(0, fa);
     // One tile: `cur` holds tile t (so its ring slot is free again), `nxt` receives tile t+1.
     // STEADY: tile t+NS exists, so exactly NS tiles are in flight at the wait and the vmcnt immediate is a compile-time
@@ -206,8 +195,8 @@ __global__ __launch_bounds__(256) void anchor_l1_mfma_kernel(AnchorMfmaArgs a) {
                         if (i * DPS + d < ND) dma(t + NS, i * DPS + d);
                 }
                 if (i == DSLOTS - 1) {
-                    if constexpr (STEADY) wait_vm<PER_TILE*(NS - 1)>();
-                    else wait_vm<0>();
+                    if constexpr (STEADY) wait_vmcnt<PER_TILE*(NS - 1)>();
+                    else wait_vmcnt<0>();
                 }
                 __builtin_amdgcn_sched_barrier(0);
             } else if (i - DSLOTS < NR) {

@@ -2,12 +2,8 @@
 //   part[ks][b][n] = sum_{k in chunk ks} W[n][k] * x[b][k]       W: 4 x (N*F/64, N*F) fp32, 4.1 GB at N=500,F=256
 // The f32 MFMA kernel of anchor_mfma.hip is matrix-pipe bound from 64 batch rows per pass (2048 SIMD cycles per 4 KB weight
 // tile against ~1300 that HBM needs).  This kernel keeps fp32 ARITHMETIC but runs it on the bf16 matrix path, which is 16 x
-// faster per product: every fp32 operand is cut - exactly, by truncation - into three bf16 pieces
-//   a = a_hi + a_mid + a_lo      (8 + 8 + 8 significand bits; a_lo is exact because the remainder has at most 8 bits left)
-// and  w * x  is accumulated (in the fp32 accumulator of v_mfma_f32_32x32x16_bf16) as the six piece products of weight
-// 2^0 .. 2^-16:  w_lo x_hi + w_hi x_lo + w_mid x_mid + w_mid x_hi + w_hi x_mid + w_hi x_hi.
-// Each bf16 x bf16 product is exact in fp32; the three dropped products are below 2^-24 |w x|, i.e. below the rounding error
-// of the fp32 FMA they replace (tests/test_hip_parity.py compares both kernels with the float64 oracle: same error level).
+// faster per product: every fp32 operand is cut into three exact bf16 pieces and w * x is accumulated as six piece products
+// (NP = 3), or into two range-scaled fp16 pieces and three products (NP = 2) - the arithmetic of pieces.hpp.
 // Cost per 4 KB weight tile and 64 batch rows: 24 MFMA x 32 = 768 cycles instead of 2048 -> the kernel is HBM-bound again.
 //
 // Data path.  The weights stay fp32 in HBM (they are the reference's checkpoint tensors) and are streamed exactly once per
@@ -22,31 +18,14 @@
 // (a) every share of x tile t+1 has landed and (b) every wave has finished reading tile t out of its slot, which is then
 // refilled with tile t+NS.  Workgroups that share an x stream (same K chunk, same frame) sit on one XCD (blockIdx.x % 8).
 #include "common.hpp"
+#include "lds_dma.hpp"
+#include "pieces.hpp"
 
-// the LDS-DMA asm below names m0 in its clobber list on purpose (it writes it)
-#pragma clang diagnostic ignored "-Winline-asm"
 #include <stdlib.h>
 
 #include <type_traits>
 
 namespace shasta {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// a = h + m + l exactly, each with at most 8 significand bits (bf16-representable by truncation)
-__device__ __forceinline__ void split3(float a, float& h, float& m, float& l) {
-    h = __uint_as_float(__float_as_uint(a) & 0xffff0000u);
-    const float r = a - h;
-    m = __uint_as_float(__float_as_uint(r) & 0xffff0000u);
-    l = r - m;
-}
-// {bf16(even), bf16(odd)} of two floats whose low 16 bits are not needed
-__device__ __forceinline__ uint32_t pack_top(float even, float odd) {
-    return __builtin_amdgcn_perm(__float_as_uint(odd), __float_as_uint(even), 0x07060302u);
-}
 
 // Largest magnitude of every row: grid (chunks, rows, sources), one atomicMax per workgroup on the bit pattern of a non-negative
 // float (order-preserving as unsigned).  `out` ([source][rows] uint32) must be zero on entry.  Rows are 16-byte aligned,
@@ -163,19 +142,8 @@ int launch_w_maxima(const float* const W[4], int H, int K, unsigned* wmax, float
     return check_launch("aux_ratio");
 }
 
-// Two-piece fp16 form (NP = 2): a * 2^e = h + l + err with h = fp16(a 2^e) and l = fp16(a 2^e - h), both rounded to nearest:
-// |err| <= 2^-24 |a 2^e|, half an ulp of the fp32 value itself.  2^e is an exact power of two - one per batch row of the
-// activations, one per weight row - that puts the row's largest magnitude into (2^13, 2^14] (range_exponent); the result row /
-// column is scaled back by 2^-(e_b + e_m) in anchor_hidden_kernel, exactly.  w * x is then the THREE products w_l x_h + w_h x_l + w_h x_h (each exact in the fp32 accumulator of
-// v_mfma_f32_32x32x16_f16; the dropped w_l x_l is below 2^-24 |w x|), half the matrix work of the six bf16 piece products.
-__device__ __forceinline__ void split2h(float a, _Float16& h, _Float16& l) {
-    h = (_Float16)a;
-    l = (_Float16)(a - (float)h);
-}
-__device__ __forceinline__ uint32_t pack_h2(_Float16 even, _Float16 odd) {
-    const f16x2 v = {even, odd};
-    return __builtin_bit_cast(uint32_t, v);
-}
+// Two-piece fp16 form (NP = 2, pieces.hpp): the range exponent 2^e is one per batch row of the activations and one per weight row;
+// the result row / column is scaled back by 2^-(e_b + e_m) in anchor_hidden_kernel, exactly.
 
 // Tried, and removed after commit 96899a8: the pre-cut fp16 form on v_mfma_f32_16x16x32_f16 instead of
 // v_mfma_f32_32x32x16_f16 - the same matrix cycles per tile (96 x 16 instead of 48 x 32 at 256 items per pass) and the same operand
@@ -218,14 +186,7 @@ __global__ __launch_bounds__(256) void split_x_kernel(SplitXArgs a) {
         if (a.NP == 2) {
             const int e = range_exponent_bits(a.xmax[src * a.B + min(brow0 + r, a.B - 1)]);
             u32x4 hi, lo;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                _Float16 h0, l0, h1, l1;
-                split2h(__builtin_ldexpf(v[2 * j], e), h0, l0);
-                split2h(__builtin_ldexpf(v[2 * j + 1], e), h1, l1);
-                hi[j] = pack_h2(h0, h1);
-                lo[j] = pack_h2(l0, l1);
-            }
+            cut2_f16x8([&](int j) { return v[j]; }, e, hi, lo);
             const size_t frag0 = ((((size_t)src * a.NBLK + bblk) * a.KT + kt0 + ktl) * (4 * a.XT)) + (size_t)(u * 2 + s) * 2;
             u32x4* o = reinterpret_cast<u32x4*>(a.xs) + frag0 * 64 + lane;
             o[0] = hi;
@@ -236,11 +197,11 @@ __global__ __launch_bounds__(256) void split_x_kernel(SplitXArgs a) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float h0, m0, l0, h1, m1, l1;
-            split3(v[2 * j], h0, m0, l0);
-            split3(v[2 * j + 1], h1, m1, l1);
-            hi[j] = pack_top(h0, h1);
-            mid[j] = pack_top(m0, m1);
-            lo[j] = pack_top(l0, l1);
+            cut3_bf16(v[2 * j], h0, m0, l0);
+            cut3_bf16(v[2 * j + 1], h1, m1, l1);
+            hi[j] = pack_bf16x2(h0, h1);
+            mid[j] = pack_bf16x2(m0, m1);
+            lo[j] = pack_bf16x2(l0, l1);
         }
         const size_t frag0 = ((((size_t)src * a.NBLK + bblk) * a.KT + kt0 + ktl) * (6 * a.XT)) + (size_t)(u * 2 + s) * 3;
         u32x4* o = reinterpret_cast<u32x4*>(a.xs) + frag0 * 64 + lane;
@@ -281,14 +242,7 @@ __global__ __launch_bounds__(256) void precut_weights_kernel(PrecutArgs a) {
         const int wex = range_exponent_bits(a.wmax[mlp * a.H + min(g * 32 + frow, a.H - 1)]);
         const float* p = &tile[frow][ktl * 32 + 16 * sstep + 8 * (lane >> 5)];
         u32x4 hi, lo;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            _Float16 h0, l0, h1, l1;
-            split2h(__builtin_ldexpf(p[2 * j], wex), h0, l0);
-            split2h(__builtin_ldexpf(p[2 * j + 1], wex), h1, l1);
-            hi[j] = pack_h2(h0, h1);
-            lo[j] = pack_h2(l0, l1);
-        }
+        cut2_f16x8([&](int j) { return p[j]; }, wex, hi, lo);
         u32x4* o = reinterpret_cast<u32x4*>(a.img) + ((((size_t)mlp * a.G + g) * a.KT + kt0 + ktl) * 4 + sstep * 2) * 64 + lane;
         o[0] = hi;
         o[64] = lo;
@@ -316,11 +270,6 @@ struct AnchorSplitArgs {
     int H, K, B, KS, Kc, KT, NBLK, groups_per_mlp;
     const unsigned* wmax;  // NP = 2: [4][H] maxima of the weight rows (launch_w_maxima, pack time)
 };
-
-template <int N>
-__device__ __forceinline__ void wait_vm_split() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // XT = batch rows per pass / 32 (2, 4 or 8); NS = ring slots; NP = pieces per operand: 3 (bf16, six products) or 2 (fp16, three)
 template <int XT, int NS, int NP, bool PRECUT = false>
@@ -382,14 +331,12 @@ __global__ __launch_bounds__(256) void anchor_l1_split_kernel(AnchorSplitArgs a)
         if (idx < 4) {
             const char* base = PRECUT ? wub + (size_t)t * 4096 + (size_t)idx * 1024 : wub + (size_t)t * 128;
             const uint32_t dst = lds0 + (uint32_t)((slot * SLOT + wid * 1024 + idx * 256) * 4);
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 nt" ::"v"(PRECUT ? woff[0] : woff[idx]), "s"(base), "s"(dst)
-                         : "memory", "m0");
+            lds_dma_x4_nt(PRECUT ? woff[0] : woff[idx], base, dst);
         } else {
             const int i = idx - 4;
             const char* base = xub + (size_t)t * (XCH * 1024) + (size_t)i * 4096;
             const uint32_t dst = lds0 + (uint32_t)((slot * SLOT + 4096 + (wid + 4 * i) * 256) * 4);
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(xoff), "s"(base), "s"(dst)
-                         : "memory", "m0");
+            lds_dma_x4(xoff, base, dst);
         }
     };
     auto issue = [&](int t, int slot) {
@@ -425,25 +372,25 @@ __global__ __launch_bounds__(256) void anchor_l1_split_kernel(AnchorSplitArgs a)
         const int s = e >> 3, d = (e & 7) >> 1;
         if constexpr (NP == 2) {
             _Float16 h, l;
-            split2h(__builtin_ldexpf(raw[e >> 2][e & 3], wex), h, l);
+            cut2_f16(__builtin_ldexpf(raw[e >> 2][e & 3], wex), h, l);
             if ((e & 1) == 0) {
                 qh = h;
                 ql = l;
             } else {
-                f.A[s][0][d] = pack_h2(qh, h);
-                f.A[s][1][d] = pack_h2(ql, l);
+                f.A[s][0][d] = pack_f16x2(qh, h);
+                f.A[s][1][d] = pack_f16x2(ql, l);
             }
         } else {
             float h, m, l;
-            split3(raw[e >> 2][e & 3], h, m, l);
+            cut3_bf16(raw[e >> 2][e & 3], h, m, l);
             if ((e & 1) == 0) {
                 ph = h;
                 pm = m;
                 pl = l;
             } else {
-                f.A[s][0][d] = pack_top(ph, h);
-                f.A[s][1][d] = pack_top(pm, m);
-                f.A[s][NP - 1][d] = pack_top(pl, l);
+                f.A[s][0][d] = pack_bf16x2(ph, h);
+                f.A[s][1][d] = pack_bf16x2(pm, m);
+                f.A[s][NP - 1][d] = pack_bf16x2(pl, l);
             }
         }
     };
@@ -451,17 +398,10 @@ __global__ __launch_bounds__(256) void anchor_l1_split_kernel(AnchorSplitArgs a)
     f32x16 acc[XT];
 #pragma unroll
     for (int u = 0; u < XT; ++u) acc[u] = f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    // piece products, small to large
-    constexpr int PW[6] = {2, 0, 1, 1, 0, 0}, PW2[3] = {1, 0, 0};
-    constexpr int PX[6] = {0, 2, 1, 0, 1, 0}, PX2[3] = {0, 1, 0};
     auto mma_one = [&](const Frag& f, int i) {
         const int s = i / (NPROD * XT), u = (i / NPROD) % XT, pr = i % NPROD;
-        if constexpr (NP == 3)
-            acc[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f.A[s][PW[pr]]),
-                                                             __builtin_bit_cast(bf16x8, f.X[u][s][PX[pr]]), acc[u], 0, 0, 0);
-        else
-            acc[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, f.A[s][PW2[pr]]),
-                                                            __builtin_bit_cast(f16x8, f.X[u][s][PX2[pr]]), acc[u], 0, 0, 0);
+        if constexpr (NP == 3) acc[u] = mfma_32x32x16_bf16(f.A[s][kProductsBf16[pr].a], f.X[u][s][kProductsBf16[pr].b], acc[u]);
+        else acc[u] = mfma_32x32x16_f16(f.A[s][kProductsF16[pr].a], f.X[u][s][kProductsF16[pr].b], acc[u]);
     };
 
     // Prologue: fill the ring, take tile 0 into registers.
@@ -471,8 +411,8 @@ __global__ __launch_bounds__(256) void anchor_l1_split_kernel(AnchorSplitArgs a)
         for (int t = 0; t < NS && t < NT; ++t, ++s) issue(t, s);
     }
     Frag fa, fb;
-    if (NT >= NS) wait_vm_split<PER_TILE*(NS - 1)>();
-    else wait_vm_split<0>();
+    if (NT >= NS) wait_vmcnt<PER_TILE*(NS - 1)>();
+    else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     if (NT > 0) {
 #pragma unroll
@@ -491,8 +431,8 @@ __global__ __launch_bounds__(256) void anchor_l1_split_kernel(AnchorSplitArgs a)
             __builtin_amdgcn_sched_barrier(0);
             if (i == 0) {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // my reads of tile t's slot have retired
-                if constexpr (STEADY) wait_vm_split<PER_TILE*(NS - 2)>();
-                else wait_vm_split<0>();
+                if constexpr (STEADY) wait_vmcnt<PER_TILE*(NS - 2)>();
+                else wait_vmcnt<0>();
                 __builtin_amdgcn_s_barrier();
                 if constexpr (!STEADY) {
                     if (t + NS < NT) issue(t + NS, sc);
@@ -601,12 +541,12 @@ __global__ __launch_bounds__(512) void anchor_l1_wide_kernel(AnchorSplitArgs a) 
             const uint32_t dst = lds0 + (uint32_t)((slot * SLOT + wid * 256) * 4);
             // (no `nt`: the workgroup of the other 512-item block reads the same fragments at about the same time on this XCD - without the
             // hint more of its reads hit the L2: 6.62 -> 6.23 GB fetched per 1024 frame-pairs, the launch time unchanged)
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(loff), "s"(base), "s"(dst) : "memory", "m0");
+            lds_dma_x4(loff, base, dst);
         } else {
             const int f = 4 * wid + idx - 1, u = f >> 1, pc = f & 1;  // fragment (item block u, piece) of the slot
             const char* base = xub + (size_t)(t >> 1) * (4 * XT * 1024) + (size_t)(((u * 2 + (t & 1)) * 2 + pc) * 1024);
             const uint32_t dst = lds0 + (uint32_t)((slot * SLOT + 2048 + f * 256) * 4);
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(loff), "s"(base), "s"(dst) : "memory", "m0");
+            lds_dma_x4(loff, base, dst);
         }
     };
     struct Frag {
@@ -623,11 +563,9 @@ __global__ __launch_bounds__(512) void anchor_l1_wide_kernel(AnchorSplitArgs a) 
     for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int u = 0; u < 4; ++u) acc[j][u] = f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    constexpr int PW2[3] = {1, 0, 0}, PX2[3] = {0, 1, 0};  // piece products, small to large
-    auto mma_one = [&](const Frag& f, int i) {             // product-major: eight independent accumulators between two products of one
+    auto mma_one = [&](const Frag& f, int i) {  // product-major: eight independent accumulators between two products of one
         const int pr = i >> 3, j = (i >> 2) & 1, u = i & 3;
-        acc[j][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, f.A[j][PW2[pr]]), __builtin_bit_cast(f16x8, f.X[u][PX2[pr]]),
-                                                           acc[j][u], 0, 0, 0);
+        acc[j][u] = mfma_32x32x16_f16(f.A[j][kProductsF16[pr].a], f.X[u][kProductsF16[pr].b], acc[j][u]);
     };
     {
         int sl = 0;
@@ -637,8 +575,8 @@ __global__ __launch_bounds__(512) void anchor_l1_wide_kernel(AnchorSplitArgs a) 
             for (int j = 0; j < ND; ++j) dma(t, sl, j);
     }
     Frag fa, fb;
-    if (NT >= NS) wait_vm_split<ND*(NS - 1)>();
-    else wait_vm_split<0>();
+    if (NT >= NS) wait_vmcnt<ND*(NS - 1)>();
+    else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     if (NT > 0) {
 #pragma unroll
@@ -655,8 +593,8 @@ __global__ __launch_bounds__(512) void anchor_l1_wide_kernel(AnchorSplitArgs a) 
             __builtin_amdgcn_sched_barrier(0);
             if (i == 0) {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // my reads of step t's slot have retired
-                if constexpr (STEADY) wait_vm_split<ND*(NS - 2)>();
-                else wait_vm_split<0>();
+                if constexpr (STEADY) wait_vmcnt<ND*(NS - 2)>();
+                else wait_vmcnt<0>();
                 __builtin_amdgcn_s_barrier();
                 if constexpr (!STEADY) {
                     if (t + NS < NT) {

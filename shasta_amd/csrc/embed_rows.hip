@@ -2,7 +2,7 @@
 // (det3d/models/tracker/shasta.py:59-60 fuse_shape.0, :86-87 res_coeff.0, :78-79 fuse_det.0, applied :286-316) in ONE kernel
 // per side:   E[row] = [ fuse_shape.0 | res_coeff.0 | fuse_det.0 ](row's features, row's box) (+ bias on the current side)
 //   columns [0, E12)   feature part  X[row][0:F] . Wemb^T   on the bf16 matrix path, every fp32 product from three exact bf16 pieces
-//                      (the arithmetic of gemm_pieces.hip / aff_pieces.hip, six products, fp32 accumulation)
+//                      (the six piece products of pieces.hpp, fp32 accumulation)
 //   columns [H1, ET)   box part      box[row][0:nf] . Wbox^T  (k-ordered fma chain, as row_prep_kernel)
 //   hand[row][13]      the row's largest |E| (range scaling of the fp16 pair kernel)
 // It replaces gemm_nt_pieces_kernel (128 x 128 tiles, both operands cut per K slice behind two barriers: 0.40 ms at 512
@@ -16,33 +16,17 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "lds_dma.hpp"
 #include "pair_layout.hpp"
-
-// the LDS-DMA asm below names m0 in its clobber list on purpose (it writes it)
-#pragma clang diagnostic ignored "-Winline-asm"
+#include "pieces.hpp"
 
 namespace shasta {
-
-typedef __bf16 ebf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t eu32x4 __attribute__((ext_vector_type(4)));
 
 // Workgroup shapes (rows = 32 x waves).  <256 rows, 8 waves>: one workgroup per CU, three ring slots.  <128, 4, two slots> at F = 256:
 // 72 KB of LDS, TWO workgroups per CU - the epilogue of one (staging, box columns, row maxima, 64 KB of stores: about as long as its
 // main loop) runs under the MFMAs of the other: 0.496 -> 0.459 ms per 1024 frame-pairs in an alternating A/B on one box
 // (tools/gpu_kernel_ab.sh; <64, 2>: 0.77, <128, 4, three slots> = one workgroup per CU again: 0.67).  Results are the same bits - a
 // wavefront's arithmetic does not depend on the shape.
-
-__device__ __forceinline__ void er_cut3(float a, float& h, float& m, float& l) {
-    h = __uint_as_float(__float_as_uint(a) & 0xffff0000u);
-    const float r = a - h;
-    m = __uint_as_float(__float_as_uint(r) & 0xffff0000u);
-    l = r - m;
-}
-__device__ __forceinline__ uint32_t er_top2(float even, float odd) {
-    return __builtin_amdgcn_perm(__float_as_uint(odd), __float_as_uint(even), 0x07060302u);
-}
-#define ER_MFMA(a, b, c) \
-    __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(ebf16x8, (a)), __builtin_bit_cast(ebf16x8, (b)), (c), 0, 0, 0)
 
 // fragments per side: [feature block NFB][k step F/16][piece 3][64 lanes] x 16 B
 size_t embed_packed_floats(int F) {
@@ -66,11 +50,11 @@ __global__ __launch_bounds__(256) void embed_pack_kernel(EmbedPackArgs a) {
         const int f = fb * 32 + (lane & 31), k0 = ks * 16 + (lane >> 5) * 8;
         float h[8], m[8], l[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) er_cut3(f < a.E12 ? a.w[side][(size_t)f * a.F + k0 + j] : 0.0f, h[j], m[j], l[j]);
-        eu32x4* dst = reinterpret_cast<eu32x4*>(a.out) + ((size_t)((side * a.nfb + fb) * nks + ks) * 3) * 64 + lane;
-        dst[0] = eu32x4{er_top2(h[0], h[1]), er_top2(h[2], h[3]), er_top2(h[4], h[5]), er_top2(h[6], h[7])};
-        dst[64] = eu32x4{er_top2(m[0], m[1]), er_top2(m[2], m[3]), er_top2(m[4], m[5]), er_top2(m[6], m[7])};
-        dst[128] = eu32x4{er_top2(l[0], l[1]), er_top2(l[2], l[3]), er_top2(l[4], l[5]), er_top2(l[6], l[7])};
+        for (int j = 0; j < 8; ++j) cut3_bf16(f < a.E12 ? a.w[side][(size_t)f * a.F + k0 + j] : 0.0f, h[j], m[j], l[j]);
+        u32x4* dst = reinterpret_cast<u32x4*>(a.out) + ((size_t)((side * a.nfb + fb) * nks + ks) * 3) * 64 + lane;
+        dst[0] = u32x4{pack_bf16x2(h[0], h[1]), pack_bf16x2(h[2], h[3]), pack_bf16x2(h[4], h[5]), pack_bf16x2(h[6], h[7])};
+        dst[64] = u32x4{pack_bf16x2(m[0], m[1]), pack_bf16x2(m[2], m[3]), pack_bf16x2(m[4], m[5]), pack_bf16x2(m[6], m[7])};
+        dst[128] = u32x4{pack_bf16x2(l[0], l[1]), pack_bf16x2(l[2], l[3]), pack_bf16x2(l[4], l[5]), pack_bf16x2(l[6], l[7])};
     }
 }
 
@@ -155,14 +139,14 @@ __global__ __launch_bounds__(64 * ER_WAVES) void embed_rows_kernel(EmbedArgs a) 
             for (int j = 0; j < 4; ++j) {
                 const char* base = xbase + (size_t)c * 128;
                 const uint32_t dst = sl + (uint32_t)((32 * wid + 8 * j) * 128);
-                asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 nt" ::"v"(xoff[j]), "s"(base), "s"(dst) : "memory", "m0");
+                lds_dma_x4_nt(xoff[j], base, dst);
             }
 #pragma unroll
             for (int j = 0; j < PW; ++j) {
                 const int f = (PW * wid + j) % S::NW, fb = f / 6, within = f % 6;  // within = 3 (k step) + piece; spare slots repeat fragments
                 const char* base = wbase + ((size_t)(fb * nks + 2 * c) * 3 + within) * 1024;
                 const uint32_t dst = sl + (uint32_t)(S::XB + f * 1024);
-                asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(woff), "s"(base), "s"(dst) : "memory", "m0");
+                lds_dma_x4(woff, base, dst);
             }
         };
         const int xrow = wid * 32 + (lane & 31), xsw = (xrow >> 1) & 7, hh2 = (lane >> 5) * 2;
@@ -171,8 +155,8 @@ __global__ __launch_bounds__(64 * ER_WAVES) void embed_rows_kernel(EmbedArgs a) 
             // every LDS read of the chunk is issued before the first use (left to itself the compiler fetched the weight fragments
             // one MFMA group at a time, each behind a full wait)
             f32x4 xr[2][2];
-            eu32x4 w[2][NFB][3];
-            const eu32x4* wf = reinterpret_cast<const eu32x4*>(sl + S::XB) + lane;
+            u32x4 w[2][NFB][3];
+            const u32x4* wf = reinterpret_cast<const u32x4*>(sl + S::XB) + lane;
 #pragma unroll
             for (int st = 0; st < 2; ++st) {
                 xr[st][0] = *reinterpret_cast<const f32x4*>(sl + xrow * 128 + ((4 * st + hh2) ^ xsw) * 16);
@@ -189,20 +173,15 @@ __global__ __launch_bounds__(64 * ER_WAVES) void embed_rows_kernel(EmbedArgs a) 
             for (int st = 0; st < 2; ++st) {
                 const f32x4 p = xr[st][0], q = xr[st][1];
                 const float v[8] = {p[0], p[1], p[2], p[3], q[0], q[1], q[2], q[3]};
-                float h[8], m[8], l[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) er_cut3(v[e], h[e], m[e], l[e]);
-                eu32x4 x[3];
-                x[0] = eu32x4{er_top2(h[0], h[1]), er_top2(h[2], h[3]), er_top2(h[4], h[5]), er_top2(h[6], h[7])};
-                x[1] = eu32x4{er_top2(m[0], m[1]), er_top2(m[2], m[3]), er_top2(m[4], m[5]), er_top2(m[6], m[7])};
-                x[2] = eu32x4{er_top2(l[0], l[1]), er_top2(l[2], l[3]), er_top2(l[4], l[5]), er_top2(l[6], l[7])};
-                // the six piece products, small to large (first operand = weight pieces: out^T[feature][row]), product-major so that
-                // consecutive MFMAs go to different accumulators
-                constexpr int PWI[6] = {2, 0, 1, 1, 0, 0}, PXI[6] = {0, 2, 1, 0, 1, 0};
+                u32x4 x[3];
+                cut3_bf16x8(v, x);
+                // the six piece products (first operand = weight pieces: out^T[feature][row]), product-major so that consecutive
+                // MFMAs go to different accumulators
 #pragma unroll
                 for (int pr = 0; pr < 6; ++pr)
 #pragma unroll
-                    for (int fb = 0; fb < NFB; ++fb) acc[fb] = ER_MFMA(w[st][fb][PWI[pr]], x[PXI[pr]], acc[fb]);
+                    for (int fb = 0; fb < NFB; ++fb)
+                        acc[fb] = mfma_32x32x16_bf16(w[st][fb][kProductsBf16[pr].a], x[kProductsBf16[pr].b], acc[fb]);
             }
         };
         // in-kernel stamps (a probe removed after commit 96899a8): 37 k cycles per workgroup in this loop, 18 k of them MFMA time; launch time with parts removed
@@ -214,8 +193,8 @@ __global__ __launch_bounds__(64 * ER_WAVES) void embed_rows_kernel(EmbedArgs a) 
         int slot = 0;
 #pragma unroll 1
         for (int c = 0; c < NC; ++c) {
-            if (NS > 2 && c + NS - 2 < NC) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER * (NS - 2)) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (NS > 2 && c + NS - 2 < NC) wait_vmcnt<PER * (NS - 2)>();
+            else wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();
             if (c + NS - 1 < NC) issue(c + NS - 1, slot == 0 ? NS - 1 : slot - 1);
             compute(slot);

@@ -483,8 +483,6 @@ __global__ __launch_bounds__(256) void gemm_strided_group_f32_kernel(GemmS g0, G
 // accumulation - master weights, activations in HBM, bias / activation epilogue and the split-K sums all stay fp32.
 // LDS rows are 32 + 8 bf16 = 80 bytes: the 16 lanes of a ds_read_b128 phase start 20 banks apart and cover all 64 banks.
 constexpr int LDH = BK + 8;
-typedef __bf16 gbf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t gu32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ uint16_t to_bf16_bits(float v) { return __builtin_bit_cast(uint16_t, (__bf16)v); }
 
@@ -536,8 +534,8 @@ __device__ __forceinline__ void gemm_strided_bf16_body(const GemmS& g, int by) {
         }
 #pragma unroll
         for (int s = 0; s < BK / 16; ++s) {
-            const gu32x4 a = *reinterpret_cast<const gu32x4*>(af + 16 * s), w = *reinterpret_cast<const gu32x4*>(wf + 16 * s);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(gbf16x8, a), __builtin_bit_cast(gbf16x8, w), acc, 0, 0, 0);
+            const u32x4 a = *reinterpret_cast<const u32x4*>(af + 16 * s), w = *reinterpret_cast<const u32x4*>(wf + 16 * s);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, w), acc, 0, 0, 0);
         }
     }
     strided_epilogue(g, acc, m0, n0, wm, wn, lane);

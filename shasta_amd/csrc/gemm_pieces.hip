@@ -1,38 +1,21 @@
 // fp32 "NT" GEMM on the bf16 matrix path:  C[m][n] = act(sum_k A[m][k] * W[n][k] + bias[n]),  A, W, C fp32.
 // Same contract as gemm_nt_f32_kernel (gemm_f32.hip) for the nn.Linear layers that are applied to many table rows
-// (det3d/models/tracker/shasta.py:59-67,86-92,94-106), but every fp32 product is formed from exact bf16 pieces like in
-// anchor_split.hip: a = a_hi + a_mid + a_lo (8 significand bits each, exact), w * a = the six piece products of weight
-// 2^0 .. 2^-16 accumulated in the fp32 accumulator of v_mfma_f32_32x32x16_bf16 (the three dropped products are below
-// 2^-24 |w a|, i.e. below the rounding of the fp32 FMA they replace).  6 bf16 MFMAs of K=16 replace 8 f32 MFMAs of K=2:
-// 2.7 x fewer matrix cycles per fp32 product.
+// (det3d/models/tracker/shasta.py:59-67,86-92,94-106), but every fp32 product is formed from exact bf16 pieces: the six piece
+// products of pieces.hpp.
 // Workgroup = 4 waves = 128 x 128 output tile (each wave 64 x 64 = 2 x 2 accumulators of 32 x 32); K is walked in 32-wide
 // slices: fp32 slices are prefetched into registers, cut on the VALU when they are stored to LDS (three bf16 images per
 // operand, row stride 80 B so that the 16 lanes of a ds_read_b128 phase cover all 64 banks), and read back as MFMA
 // fragments (8 consecutive k per lane).  Two workgroups per CU (60 KB of LDS each): one cuts while the other multiplies.
 // (A one-workgroup-per-CU form with double-buffered LDS, one barrier per slice and the cut interleaved behind the MFMA chains
 // of the same wave measured 61 us instead of 39.5 us on 64 256 x 128 x 256: the second workgroup hides more than the pipeline.)
-#include "common.hpp"
+#include "pieces.hpp"
 
 namespace shasta {
-
-typedef __bf16 pbf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t pu32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t pu32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int PM = 128, PN = 128, PK = 32;
 constexpr int PROW = 80;                   // bytes per LDS row of one piece image: 32 bf16 + 16 B pad
 constexpr int PIMG = PM * PROW;            // one piece image of one operand
 static_assert(PM == PN, "both operands use the same staging code");
-
-__device__ __forceinline__ void cut3(float a, float& h, float& m, float& l) {
-    h = __uint_as_float(__float_as_uint(a) & 0xffff0000u);
-    const float r = a - h;
-    m = __uint_as_float(__float_as_uint(r) & 0xffff0000u);
-    l = r - m;
-}
-__device__ __forceinline__ uint32_t top2(float even, float odd) {
-    return __builtin_amdgcn_perm(__float_as_uint(odd), __float_as_uint(even), 0x07060302u);
-}
 
 // 128 rows x 32 k of fp32 -> registers (4 float4 per thread); rows >= `rows` and k >= K read as zero
 template <bool VEC>
@@ -59,10 +42,10 @@ __device__ __forceinline__ void pieces_store(char* img, int tid, const f32x4 (&r
         char* dst = img + (idx >> 3) * PROW + (idx & 7) * 8;
         float h[4], m[4], l[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) cut3(reg[i][j], h[j], m[j], l[j]);
-        *reinterpret_cast<pu32x2*>(dst) = pu32x2{top2(h[0], h[1]), top2(h[2], h[3])};
-        *reinterpret_cast<pu32x2*>(dst + PIMG) = pu32x2{top2(m[0], m[1]), top2(m[2], m[3])};
-        *reinterpret_cast<pu32x2*>(dst + 2 * PIMG) = pu32x2{top2(l[0], l[1]), top2(l[2], l[3])};
+        for (int j = 0; j < 4; ++j) cut3_bf16(reg[i][j], h[j], m[j], l[j]);
+        *reinterpret_cast<u32x2*>(dst) = u32x2{pack_bf16x2(h[0], h[1]), pack_bf16x2(h[2], h[3])};
+        *reinterpret_cast<u32x2*>(dst + PIMG) = u32x2{pack_bf16x2(m[0], m[1]), pack_bf16x2(m[2], m[3])};
+        *reinterpret_cast<u32x2*>(dst + 2 * PIMG) = u32x2{pack_bf16x2(l[0], l[1]), pack_bf16x2(l[2], l[3])};
     }
 }
 
@@ -98,8 +81,6 @@ __global__ __launch_bounds__(256) void gemm_nt_pieces_kernel(GemmPieces g) {
     // fragment of row-block i, k-step s, piece p: 8 consecutive k of row 64*w + 32*i + (lane & 31), k = 16 s + 8 (lane >> 5)
     const char* af = s_a + (wm * 64 + (lane & 31)) * PROW + (lane >> 5) * 16;
     const char* wf = s_w + (wn * 64 + (lane & 31)) * PROW + (lane >> 5) * 16;
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0};  // piece products, small to large
-    constexpr int PB[6] = {0, 2, 1, 0, 1, 0};
     for (int kt = 0; kt < nk; ++kt) {
         __syncthreads();  // previous slice fully consumed
         pieces_store(s_a, tid, ra);
@@ -111,13 +92,13 @@ __global__ __launch_bounds__(256) void gemm_nt_pieces_kernel(GemmPieces g) {
         }
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            pu32x4 fa[2][3], fw[2][3];
+            u32x4 fa[2][3], fw[2][3];
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int p = 0; p < 3; ++p) {
-                    fa[i][p] = *reinterpret_cast<const pu32x4*>(af + p * PIMG + i * 32 * PROW + s * 32);
-                    fw[i][p] = *reinterpret_cast<const pu32x4*>(wf + p * PIMG + i * 32 * PROW + s * 32);
+                    fa[i][p] = *reinterpret_cast<const u32x4*>(af + p * PIMG + i * 32 * PROW + s * 32);
+                    fw[i][p] = *reinterpret_cast<const u32x4*>(wf + p * PIMG + i * 32 * PROW + s * 32);
                 }
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -125,8 +106,7 @@ __global__ __launch_bounds__(256) void gemm_nt_pieces_kernel(GemmPieces g) {
                 for (int j = 0; j < 2; ++j)
 #pragma unroll
                     for (int q = 0; q < 6; ++q)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(pbf16x8, fa[i][PA[q]]),
-                                                                            __builtin_bit_cast(pbf16x8, fw[j][PB[q]]), acc[i][j], 0, 0, 0);
+                        acc[i][j] = mfma_32x32x16_bf16(fa[i][kProductsBf16[q].a], fw[j][kProductsBf16[q].b], acc[i][j]);
         }
     }
     // C/D map of a 32x32 accumulator: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)

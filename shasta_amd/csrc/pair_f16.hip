@@ -3,9 +3,8 @@
 //
 // Why only the second layers: the activations h1 = relu(UP[t] + UC[d]) exist per pair, so cutting them into pieces is VALU work
 // per pair; it pays where one cut value feeds 16 multiply-adds (layer 2: 64 -> 16, 32 -> 16, 32 -> 8) and not for the narrow
-// layers behind it.  Arithmetic (the two-piece fp16 form of anchor_split.hip): a * 2^e = h + l with h = fp16(a 2^e),
-// l = fp16(a 2^e - h), both rounded to nearest (|err| <= 2^-24 |a 2^e|); w * a = w_l a_h + w_h a_l + w_h a_h, three
-// v_mfma_f32_16x16x32_f16 instead of sixteen f32 4x4x1 MFMA slots per 16 x 16 x 32 block; fp32 accumulation.
+// layers behind it.  Arithmetic: the two-piece fp16 form of pieces.hpp (three products), three v_mfma_f32_16x16x32_f16 instead of
+// sixteen f32 4x4x1 MFMA slots per 16 x 16 x 32 block; fp32 accumulation.
 //
 // Layouts.  A wave owns 64 detections x a range of tracks (as before).  Per track:
 //  (1) four sub-steps of 16 detections in the MFMA layout lane = (pair p = lane & 15, k block kb = lane >> 4): the lane forms
@@ -22,18 +21,13 @@
 // second-layer weights are cut once at pack time with one exponent per MLP (pair_f16_pack_kernel).
 #include "common.hpp"
 #include "pair_layout.hpp"
+#include "pieces.hpp"
 
 #include <type_traits>
 
 namespace shasta {
 
-typedef _Float16 ph16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 ph16x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t pu4 __attribute__((ext_vector_type(4)));
-
 #define MFMA4(a, b, c) __builtin_amdgcn_mfma_f32_4x4x1f32((a), (b), (c), 0, 0, 0)
-#define MFMA16H(a, b, c) \
-    __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(ph16x8, (a)), __builtin_bit_cast(ph16x8, (b)), (c), 0, 0, 0)
 
 template <int F, int L>
 struct A4h {
@@ -41,32 +35,8 @@ struct A4h {
     static constexpr int NOB = a4_nob(F, L), KG = a4_kg(F, L), OFF = a4_offset(F, L), KIN = D.kin, BIAS = NOB * KG * 16;
 };
 
-// HAZARD RULE for the three asm helpers below: the compiler inserts the wait states a VALU result needs before an MFMA or a
-// half-register reader consumes it only for its OWN instructions, not around inline asm.  Every result of these helpers must
-// therefore pass through a compiler-generated VALU instruction (here: the packed multiply, v_cvt_pk_f16_f32) before it reaches an
-// MFMA operand; feeding one straight into an MFMA needs an explicit "s_nop 1" (the clamp-fma tried in pair_mfma4).
-// {clamp01(a0 * c + b0), clamp01(a1 * c + b1)}: with a, b pre-scaled so that every sum is at most 1, the clamp IS the ReLU
-typedef float pf2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ pf2 fma2_relu01(pf2 a, pf2 c, pf2 b) {
-    pf2 r;
-    asm("v_pk_fma_f32 %0, %1, %2, %3 clamp" : "=v"(r) : "v"(a), "v"(c), "v"(b));
-    return r;
-}
-// x - h (exact in fp32) with h = the low / high half of a packed f16 pair read as an f16 operand
-__device__ __forceinline__ float res_lo(float x, uint32_t hpk) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(r) : "v"(x), "v"(hpk));
-    return r;
-}
-__device__ __forceinline__ float res_hi(float x, uint32_t hpk) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r) : "v"(x), "v"(hpk));
-    return r;
-}
-__device__ __forceinline__ uint32_t cvt2(float a, float b) {
-    const ph16x2 v = {(_Float16)a, (_Float16)b};
-    return __builtin_bit_cast(uint32_t, v);
-}
+// (fma2_relu01, f16_res_lo / _hi: every result passes through the packed multiply or v_cvt_pk_f16_f32 before it reaches an MFMA -
+// hazard rule of pieces.hpp)
 
 // ---- pack: the three second layers as A operands of v_mfma_f32_16x16x32_f16 -----------------------------------------------
 // fragments (1 KB each = [64 lanes][8 fp16]): 0 fuse_shape.2 (16 x 32) | 1, 2 res_coeff.2 (16 x 64, two k steps) | 3 fuse_det.2
@@ -89,21 +59,7 @@ __global__ __launch_bounds__(256) void pair_f16_pack_kernel(PairF16PackArgs a) {
     const int tid = threadIdx.x;
     const float* W[3] = {a.w_fs2, a.w_rc2, a.w_fd2};
     const int cnt[3] = {16 * 32, 16 * 64, 8 * 32};
-    for (int m = 0; m < 3; ++m) {
-        float mx = 0.0f;
-        for (int i = tid; i < cnt[m]; i += 256) mx = fmaxf(mx, fabsf(W[m][i]));
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-        if ((tid & 63) == 0) red[m][tid >> 6] = mx;
-    }
-    __syncthreads();
-    if (tid < 3) {
-        const float mx = fmaxf(fmaxf(red[tid][0], red[tid][1]), fmaxf(red[tid][2], red[tid][3]));
-        ex[tid] = range_exponent_bits(__float_as_uint(mx));
-        reinterpret_cast<int*>(a.out)[P16_FRAG_DW + tid] = ex[tid];
-    }
-    if (tid == 3) a.out[P16_FRAG_DW + 3] = 0;
-    __syncthreads();
+    pair2_range_exponents(W, cnt, a.out, P16_FRAG_DW, red, ex);
     const int lane = tid & 63, frag = tid >> 6;  // 4 fragments, one wave each
     const int i = lane & 15, kb = lane >> 4;
     const int mlp = frag == 0 ? 0 : frag == 3 ? 2 : 1;
@@ -111,16 +67,16 @@ __global__ __launch_bounds__(256) void pair_f16_pack_kernel(PairF16PackArgs a) {
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = i < rows ? __builtin_ldexpf(W[mlp][i * kin + 32 * ks + 8 * kb + j], ex[mlp]) : 0.0f;
-    pu4 hi, lo;
+    u32x4 hi, lo;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const _Float16 h0 = (_Float16)v[2 * j], h1 = (_Float16)v[2 * j + 1];
-        const ph16x2 hh = {h0, h1};
+        const f16x2 hh = {h0, h1};
         hi[j] = __builtin_bit_cast(uint32_t, hh);
-        lo[j] = cvt2(v[2 * j] - (float)h0, v[2 * j + 1] - (float)h1);
+        lo[j] = cvt_f16x2(v[2 * j] - (float)h0, v[2 * j + 1] - (float)h1);
     }
-    reinterpret_cast<pu4*>(a.out)[(0 * 4 + frag) * 64 + lane] = hi;
-    reinterpret_cast<pu4*>(a.out)[(1 * 4 + frag) * 64 + lane] = lo;
+    reinterpret_cast<u32x4*>(a.out)[(0 * 4 + frag) * 64 + lane] = hi;
+    reinterpret_cast<u32x4*>(a.out)[(1 * 4 + frag) * 64 + lane] = lo;
 }
 
 int pair_f16_pack(const shasta_weights* w, float* out, hipStream_t st) {
@@ -280,11 +236,11 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
         }
     }
     // second-layer weight pieces: 4 fragments x {high, low}, registers for the whole kernel
-    pu4 wh[4], wl[4];
+    u32x4 wh[4], wl[4];
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
-        wh[f] = reinterpret_cast<const pu4*>(p16)[(0 * 4 + f) * 64 + lane];
-        wl[f] = reinterpret_cast<const pu4*>(p16)[(1 * 4 + f) * 64 + lane];
+        wh[f] = reinterpret_cast<const u32x4*>(p16)[(0 * 4 + f) * 64 + lane];
+        wl[f] = reinterpret_cast<const u32x4*>(p16)[(1 * 4 + f) * 64 + lane];
     }
     const int ew_fs = reinterpret_cast<const int*>(p16)[P16_FRAG_DW + 0], ew_rc = reinterpret_cast<const int*>(p16)[P16_FRAG_DW + 1],
               ew_fd = reinterpret_cast<const int*>(p16)[P16_FRAG_DW + 2];
@@ -333,10 +289,10 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
         typedef _Float16 ph2 __attribute__((ext_vector_type(2)));
         bool finite_bound;
         int e1 = 0;
-        pf2 cs2 = {0.0f, 0.0f};
-        const pf2 c14 = {16384.0f, 16384.0f};
-        pf2 upv[GRID ? 1 : 16];   // !GRID: this lane's UP values, scaled
-        pu4 uph[GRID ? 4 : 1], upl[GRID ? 4 : 1];  // GRID: this lane's UP pieces, 8 per k step
+        f32x2 cs2 = {0.0f, 0.0f};
+        const f32x2 c14 = {16384.0f, 16384.0f};
+        f32x2 upv[GRID ? 1 : 16];   // !GRID: this lane's UP values, scaled
+        u32x4 uph[GRID ? 4 : 1], upl[GRID ? 4 : 1];  // GRID: this lane's UP pieces, 8 per k step
         if constexpr (!GRID) {
             // the track's scale: every h1 of this track and tile is at most max |UP[t]| + max |UC|
             // Non-finite embeddings: the clamp of the packed fma below turns a NaN into 0 and saturates an infinity at 1, so they would
@@ -348,17 +304,17 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
             // h1 = relu(UP + UC) is formed as clamp01(UC cs + UP cs) with cs = 2^(e1 - 14): every sum is at most 1 after the scaling
             // (exact, a power of two), so the clamp of one packed fma is the ReLU of two values; the conversion multiplies by 2^14.
             const float cs = __builtin_ldexpf(1.0f, e1 - 14);
-            cs2 = pf2{cs, cs};
+            cs2 = f32x2{cs, cs};
             // this lane's UP values, scaled: 8 per k step (the same address in the 16 lanes of a k block: LDS broadcast).  (Scaling the row
             // ONCE in place in LDS - 2 packed multiplies per track instead of 16, as pair_f16w.hip does - measured slower here: 4.06 - 4.13 ->
             // 4.18 - 4.21 ms at 512 frame-pairs: the write-read round trip through LDS sits on this kernel's critical path.)
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 const f32x4 a = *reinterpret_cast<const lf32x4*>(up + 32 * s + 8 * kb), c = *reinterpret_cast<const lf32x4*>(up + 32 * s + 8 * kb + 4);
-                upv[4 * s] = pf2{a[0], a[1]} * cs2;
-                upv[4 * s + 1] = pf2{a[2], a[3]} * cs2;
-                upv[4 * s + 2] = pf2{c[0], c[1]} * cs2;
-                upv[4 * s + 3] = pf2{c[2], c[3]} * cs2;
+                upv[4 * s] = f32x2{a[0], a[1]} * cs2;
+                upv[4 * s + 1] = f32x2{a[2], a[3]} * cs2;
+                upv[4 * s + 2] = f32x2{c[0], c[1]} * cs2;
+                upv[4 * s + 3] = f32x2{c[2], c[3]} * cs2;
             }
         } else {
             finite_bound = grid_finite;
@@ -366,8 +322,8 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
             // into the wave's piece rows; every lane then reads its 8 values per k step back (LDS broadcast within a k block)
             uint32_t* my_p = s_upp + wid * 128;  // [high 64 words | low 64 words]
             {
-                typedef __attribute__((address_space(3))) pf2 lpf2;
-                const pf2 v = *reinterpret_cast<const lpf2*>(up + 2 * lane);
+                typedef __attribute__((address_space(3))) f32x2 lf32x2;
+                const f32x2 v = *reinterpret_cast<const lf32x2*>(up + 2 * lane);
                 const int ex = lane < 16 ? ge[0] : lane < 48 ? ge[1] : ge[2];
                 const float s0 = __builtin_ldexpf(v[0], ex), s1 = __builtin_ldexpf(v[1], ex);
                 const float h0 = rintf(s0), h1v = rintf(s1);
@@ -378,8 +334,8 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
             }
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
-                uph[s] = *reinterpret_cast<const pu4*>(my_p + 16 * s + 4 * kb);
-                upl[s] = *reinterpret_cast<const pu4*>(my_p + 64 + 16 * s + 4 * kb);
+                uph[s] = *reinterpret_cast<const u32x4*>(my_p + 16 * s + 4 * kb);
+                upl[s] = *reinterpret_cast<const u32x4*>(my_p + 64 + 16 * s + 4 * kb);
             }
         }
         // Software pipeline over the four sub-steps: the UC reads of sub-step s+1 are issued before the arithmetic of sub-step s,
@@ -391,8 +347,8 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
                 const uint32_t* lr = s_ucl + (16 * sub + p) * (GR_ROW / 2) + 4 * kb;
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
-                    u[s] = __builtin_bit_cast(f32x4, *reinterpret_cast<const pu4*>(hr + 16 * s));
-                    u[4 + s] = __builtin_bit_cast(f32x4, *reinterpret_cast<const pu4*>(lr + 16 * s));
+                    u[s] = __builtin_bit_cast(f32x4, *reinterpret_cast<const u32x4*>(hr + 16 * s));
+                    u[4 + s] = __builtin_bit_cast(f32x4, *reinterpret_cast<const u32x4*>(lr + 16 * s));
                 }
                 return;
             }
@@ -408,21 +364,21 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
                 u[2 * s + 1] = *reinterpret_cast<const f32x4*>(ucr + 8 * s + 4);
             }
         };
-        auto cut = [&](const f32x4 (&u)[8], pu4 (&xh)[4], pu4 (&xl)[4]) {
+        auto cut = [&](const f32x4 (&u)[8], u32x4 (&xh)[4], u32x4 (&xl)[4]) {
             if constexpr (GRID) {
                 // pieces of relu(UP + UC): exact packed adds, then h' = max(h, -1), l' = max(l, -h'); on whole 8-halves vectors (the
                 // compiler lowers them to v_pk_add_f16 / v_pk_max_f16 with the negation as an operand modifier; written dword by dword
                 // through bit casts of vector elements hipcc 7.2 computed element 0 only and replicated it)
                 const _Float16 m1 = (_Float16)-1.0f;
-                const ph16x8 neg1 = {m1, m1, m1, m1, m1, m1, m1, m1};
+                const f16x8 neg1 = {m1, m1, m1, m1, m1, m1, m1, m1};
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
-                    const ph16x8 h = __builtin_bit_cast(ph16x8, u[s]) + __builtin_bit_cast(ph16x8, uph[s]);
-                    const ph16x8 l = __builtin_bit_cast(ph16x8, u[4 + s]) + __builtin_bit_cast(ph16x8, upl[s]);
-                    const ph16x8 h2 = __builtin_elementwise_max(h, neg1);
-                    const ph16x8 l2 = __builtin_elementwise_max(l, -h2);
-                    xh[s] = __builtin_bit_cast(pu4, h2);
-                    xl[s] = __builtin_bit_cast(pu4, l2);
+                    const f16x8 h = __builtin_bit_cast(f16x8, u[s]) + __builtin_bit_cast(f16x8, uph[s]);
+                    const f16x8 l = __builtin_bit_cast(f16x8, u[4 + s]) + __builtin_bit_cast(f16x8, upl[s]);
+                    const f16x8 h2 = __builtin_elementwise_max(h, neg1);
+                    const f16x8 l2 = __builtin_elementwise_max(l, -h2);
+                    xh[s] = __builtin_bit_cast(u32x4, h2);
+                    xl[s] = __builtin_bit_cast(u32x4, l2);
                 }
                 return;
             }
@@ -435,30 +391,30 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
                     // its conversion.  Only full-register writes: the v_fma_mixlo / mixhi_f16 pair this replaces cost 17.8 cycles per
                     // two values against 13.4 for multiply + convert (tools/probes/valu_cost_probe.hip) and needed a hand-placed wait
                     // state between a half-register write and its reader that the compiler does not insert around inline asm.
-                    const pf2 sa = fma2_relu01(pf2{uu[0], uu[1]}, cs2, upv[4 * s + 2 * j2]) * c14;
-                    const pf2 sb = fma2_relu01(pf2{uu[2], uu[3]}, cs2, upv[4 * s + 2 * j2 + 1]) * c14;
-                    const uint32_t hA = cvt2(sa[0], sa[1]), hB = cvt2(sb[0], sb[1]);
+                    const f32x2 sa = fma2_relu01(f32x2{uu[0], uu[1]}, cs2, upv[4 * s + 2 * j2]) * c14;
+                    const f32x2 sb = fma2_relu01(f32x2{uu[2], uu[3]}, cs2, upv[4 * s + 2 * j2 + 1]) * c14;
+                    const uint32_t hA = cvt_f16x2(sa[0], sa[1]), hB = cvt_f16x2(sb[0], sb[1]);
                     xh[s][2 * j2] = hA;
                     xh[s][2 * j2 + 1] = hB;
-                    xl[s][2 * j2] = cvt2(res_lo(sa[0], hA), res_hi(sa[1], hA));
-                    xl[s][2 * j2 + 1] = cvt2(res_lo(sb[0], hB), res_hi(sb[1], hB));
+                    xl[s][2 * j2] = cvt_f16x2(f16_res_lo(sa[0], hA), f16_res_hi(sa[1], hA));
+                    xl[s][2 * j2 + 1] = cvt_f16x2(f16_res_lo(sb[0], hB), f16_res_hi(sb[1], hB));
                 }
             }
         };
-        auto mma = [&](const pu4 (&xh)[4], const pu4 (&xl)[4], f32x4& a_fs, f32x4& a_rc, f32x4& a_fd) {
+        auto mma = [&](const u32x4 (&xh)[4], const u32x4 (&xl)[4], f32x4& a_fs, f32x4& a_rc, f32x4& a_fd) {
             a_fs = a_rc = a_fd = zero4;
-            a_fs = MFMA16H(wl[0], xh[0], a_fs);
-            a_rc = MFMA16H(wl[1], xh[1], a_rc);
-            a_fd = MFMA16H(wl[3], xh[3], a_fd);
-            a_fs = MFMA16H(wh[0], xl[0], a_fs);
-            a_rc = MFMA16H(wh[1], xl[1], a_rc);
-            a_fd = MFMA16H(wh[3], xl[3], a_fd);
-            a_rc = MFMA16H(wl[2], xh[2], a_rc);
-            a_fs = MFMA16H(wh[0], xh[0], a_fs);
-            a_fd = MFMA16H(wh[3], xh[3], a_fd);
-            a_rc = MFMA16H(wh[2], xl[2], a_rc);
-            a_rc = MFMA16H(wh[1], xh[1], a_rc);
-            a_rc = MFMA16H(wh[2], xh[2], a_rc);
+            a_fs = mfma_16x16x32_f16(wl[0], xh[0], a_fs);
+            a_rc = mfma_16x16x32_f16(wl[1], xh[1], a_rc);
+            a_fd = mfma_16x16x32_f16(wl[3], xh[3], a_fd);
+            a_fs = mfma_16x16x32_f16(wh[0], xl[0], a_fs);
+            a_rc = mfma_16x16x32_f16(wh[1], xl[1], a_rc);
+            a_fd = mfma_16x16x32_f16(wh[3], xl[3], a_fd);
+            a_rc = mfma_16x16x32_f16(wl[2], xh[2], a_rc);
+            a_fs = mfma_16x16x32_f16(wh[0], xh[0], a_fs);
+            a_fd = mfma_16x16x32_f16(wh[3], xh[3], a_fd);
+            a_rc = mfma_16x16x32_f16(wh[2], xl[2], a_rc);
+            a_rc = mfma_16x16x32_f16(wh[1], xh[1], a_rc);
+            a_rc = mfma_16x16x32_f16(wh[2], xh[2], a_rc);
         };
         // (storing a sub-step's results behind the NEXT sub-step's MFMAs instead of right behind their own - where each store waits
         // 5 - 7 idle states for its accumulator - measured slower: 4.20 -> 4.30 ms; the compiler fills those states elsewhere)
@@ -471,7 +427,7 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
         };
         {
             f32x4 ua[8], ub[8];
-            pu4 xha[4], xla[4], xhb[4], xlb[4];
+            u32x4 xha[4], xla[4], xhb[4], xlb[4];
             f32x4 fsA, rcA, fdA, fsB, rcB, fdB;
             load_uc(0, ua);
             load_uc(1, ub);
@@ -508,9 +464,9 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
             const float* b_fd = s_a4 + A4h<F, L_FD2>::OFF + A4h<F, L_FD2>::BIAS;
             // descale + bias as packed fmas (two values per 5-cycle slot instead of one per 6), ReLU right behind them
             auto fma4 = [&](const f32x4& v, float sc, const f32x4& bb) {
-                const pf2 s2 = {sc, sc};
-                const pf2 lo = __builtin_elementwise_fma(pf2{v[0], v[1]}, s2, pf2{bb[0], bb[1]});
-                const pf2 hi = __builtin_elementwise_fma(pf2{v[2], v[3]}, s2, pf2{bb[2], bb[3]});
+                const f32x2 s2 = {sc, sc};
+                const f32x2 lo = __builtin_elementwise_fma(f32x2{v[0], v[1]}, s2, f32x2{bb[0], bb[1]});
+                const f32x2 hi = __builtin_elementwise_fma(f32x2{v[2], v[3]}, s2, f32x2{bb[2], bb[3]});
                 // (fmaxf, not the NaN-propagating relu_nan of the other kernels: non-finite inputs never get here - finite_bound above -
                 // and v_maximum3_f32 in this loop measured 1 - 3 % of the kernel: 4.39 - 4.43 -> 4.45 - 4.56 ms)
                 return f32x4{fmaxf(lo[0], 0.0f), fmaxf(lo[1], 0.0f), fmaxf(hi[0], 0.0f), fmaxf(hi[1], 0.0f)};

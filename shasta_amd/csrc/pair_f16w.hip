@@ -31,19 +31,13 @@
 // -68 instructions) moved the time by 1.6 %.
 #include "common.hpp"
 #include "pair_layout.hpp"
+#include "pieces.hpp"
 
 #include <type_traits>
 
 namespace shasta {
 
-typedef _Float16 wh16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 wh16x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t wu4 __attribute__((ext_vector_type(4)));
-typedef float wf2 __attribute__((ext_vector_type(2)));
-
 #define MFMA4W(a, b, c) __builtin_amdgcn_mfma_f32_4x4x1f32((a), (b), (c), 0, 0, 0)
-#define MFMA32H(a, b, c) \
-    __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wh16x8, (a)), __builtin_bit_cast(wh16x8, (b)), (c), 0, 0, 0)
 
 template <int F>
 struct PW {
@@ -71,30 +65,11 @@ struct A4w {
     static constexpr int NOB = a4_nob(F, L), KG = a4_kg(F, L), OFF = a4_offset(F, L), KIN = D.kin, BIAS = NOB * KG * 16;
 };
 
-// (the three asm helpers and their hazard rule: pair_f16.hip)
-__device__ __forceinline__ wf2 w_fma2_relu01(wf2 a, wf2 c, wf2 b) {
-    wf2 r;
-    asm("v_pk_fma_f32 %0, %1, %2, %3 clamp" : "=v"(r) : "v"(a), "v"(c), "v"(b));
-    return r;
-}
-__device__ __forceinline__ wf2 w_mul2(wf2 a, wf2 c) {  // (the compiler splits a wf2 product of an asm result into two v_mul_f32)
-    wf2 r;
+// (the asm helpers of pieces.hpp and w_mul2 below: hazard rule of pieces.hpp)
+__device__ __forceinline__ f32x2 w_mul2(f32x2 a, f32x2 c) {  // (the compiler splits an f32x2 product of an asm result into two v_mul_f32)
+    f32x2 r;
     asm("v_pk_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(c));
     return r;
-}
-__device__ __forceinline__ float w_res_lo(float x, uint32_t hpk) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(r) : "v"(x), "v"(hpk));
-    return r;
-}
-__device__ __forceinline__ float w_res_hi(float x, uint32_t hpk) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r) : "v"(x), "v"(hpk));
-    return r;
-}
-__device__ __forceinline__ uint32_t w_cvt2(float a, float b) {
-    const wh16x2 v = {(_Float16)a, (_Float16)b};
-    return __builtin_bit_cast(uint32_t, v);
 }
 
 // ---- pack: the three second layers as A operands of v_mfma_f32_32x32x16_f16 -------------------------------------------------
@@ -117,21 +92,7 @@ __global__ __launch_bounds__(256) void pair_f16w_pack_kernel(PairF16WPackArgs a)
     const int tid = threadIdx.x;
     const float* Wm[3] = {a.w_fs2, a.w_rc2, a.w_fd2};
     const int cnt[3] = {W::H2 * W::H1, W::R2 * W::R1, 8 * 32};
-    for (int m = 0; m < 3; ++m) {
-        float mx = 0.0f;
-        for (int i = tid; i < cnt[m]; i += 256) mx = fmaxf(mx, fabsf(Wm[m][i]));
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-        if ((tid & 63) == 0) red[m][tid >> 6] = mx;
-    }
-    __syncthreads();
-    if (tid < 3) {
-        const float mx = fmaxf(fmaxf(red[tid][0], red[tid][1]), fmaxf(red[tid][2], red[tid][3]));
-        ex[tid] = range_exponent_bits(__float_as_uint(mx));
-        reinterpret_cast<int*>(a.out)[W::FRAG_DW + tid] = ex[tid];
-    }
-    if (tid == 3) a.out[W::FRAG_DW + 3] = 0;
-    __syncthreads();
+    pair2_range_exponents(Wm, cnt, a.out, W::FRAG_DW, red, ex);
     const int lane = tid & 63, m = lane & 31, kb = lane >> 5;
     for (int item = tid >> 6; item < 2 * W::NKS; item += 4) {
         const int ks = item >> 1, blk = item & 1;
@@ -150,16 +111,16 @@ __global__ __launch_bounds__(256) void pair_f16w_pack_kernel(PairF16WPackArgs a)
             }
             v[j] = x;
         }
-        wu4 hi, lo;
+        u32x4 hi, lo;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const _Float16 h0 = (_Float16)v[2 * j], h1 = (_Float16)v[2 * j + 1];
-            const wh16x2 hh = {h0, h1};
+            const f16x2 hh = {h0, h1};
             hi[j] = __builtin_bit_cast(uint32_t, hh);
-            lo[j] = w_cvt2(v[2 * j] - (float)h0, v[2 * j + 1] - (float)h1);
+            lo[j] = cvt_f16x2(v[2 * j] - (float)h0, v[2 * j + 1] - (float)h1);
         }
-        reinterpret_cast<wu4*>(a.out)[(0 * W::NFRAG + frag) * 64 + lane] = hi;
-        reinterpret_cast<wu4*>(a.out)[(1 * W::NFRAG + frag) * 64 + lane] = lo;
+        reinterpret_cast<u32x4*>(a.out)[(0 * W::NFRAG + frag) * 64 + lane] = hi;
+        reinterpret_cast<u32x4*>(a.out)[(1 * W::NFRAG + frag) * 64 + lane] = lo;
     }
 }
 
@@ -191,7 +152,7 @@ __global__ __launch_bounds__(64 * PWK_WPB) __attribute__((amdgpu_waves_per_eu(2,
     extern __shared__ __attribute__((aligned(16))) float s_dynw[];
     float* s_a4 = s_dynw;                          // [NA4] 4x4x1 operand table (layers 3-4 and the layer-2 biases)
     float* s_up = s_dynw + ((NA4 + 3) & ~3);       // [WPB][3 steps][2 rows][PWK_SLOT]
-    wu4* s_w = reinterpret_cast<wu4*>(s_up + PWK_WPB * 6 * PWK_SLOT);  // [piece][fragment][lane] second-layer weight pieces
+    u32x4* s_w = reinterpret_cast<u32x4*>(s_up + PWK_WPB * 6 * PWK_SLOT);  // [piece][fragment][lane] second-layer weight pieces
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     int lbx, by, b;
@@ -228,8 +189,8 @@ __global__ __launch_bounds__(64 * PWK_WPB) __attribute__((amdgpu_waves_per_eu(2,
     for (int off = 16; off > 0; off >>= 1) mc = absmax_keep_nan(mc, __shfl_xor(mc, off, 64));  // (both halves hold the same 32 rows)
     const float dnm = denom[(size_t)b * D + dcl], rdn = 1.0f / dnm;
     // second-layer weight pieces: registers for the whole kernel
-    for (int e = tid; e < 2 * NFRAG * 64; e += 64 * PWK_WPB) s_w[e] = reinterpret_cast<const wu4*>(p16)[e];
-    const wu4* my_w = s_w + lane;
+    for (int e = tid; e < 2 * NFRAG * 64; e += 64 * PWK_WPB) s_w[e] = reinterpret_cast<const u32x4*>(p16)[e];
+    const u32x4* my_w = s_w + lane;
     const int ew_fs = reinterpret_cast<const int*>(p16)[W::FRAG_DW + 0], ew_rc = reinterpret_cast<const int*>(p16)[W::FRAG_DW + 1],
               ew_fd = reinterpret_cast<const int*>(p16)[W::FRAG_DW + 2];
     __syncthreads();
@@ -259,7 +220,7 @@ __global__ __launch_bounds__(64 * PWK_WPB) __attribute__((amdgpu_waves_per_eu(2,
         dma_up(t_beg + 2, 2);
         dma_up(t_beg + 3, 3);
     }
-    const wf2 c14 = {16384.0f, 16384.0f};
+    const f32x2 c14 = {16384.0f, 16384.0f};
     int step = 0;
     for (int t = t_beg; t < t_end; t += 2, ++step) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -273,7 +234,7 @@ __global__ __launch_bounds__(64 * PWK_WPB) __attribute__((amdgpu_waves_per_eu(2,
         const float boundA = upA[ET + 13] + mc, boundB = upB[ET + 13] + mc;
         const int e1A = range_exponent_bits(__float_as_uint(boundA)), e1B = range_exponent_bits(__float_as_uint(boundB));
         const float csA = __builtin_ldexpf(1.0f, e1A - 14), csB = __builtin_ldexpf(1.0f, e1B - 14);
-        const wf2 cs2A = {csA, csA}, cs2B = {csB, csB};
+        const f32x2 cs2A = {csA, csA}, cs2B = {csB, csB};
         // the two UP rows are scaled ONCE, in place (lane i takes float4 i of both; the lanes behind the row repeat its last float4):
         // 4 packed multiplies per step instead of the 72 that every lane would spend on the values it reads back below
         {
@@ -282,32 +243,32 @@ __global__ __launch_bounds__(64 * PWK_WPB) __attribute__((amdgpu_waves_per_eu(2,
             wlf32x4* pa = (wlf32x4*)(unsigned long long)(upo + 4 * q);
             wlf32x4* pb = (wlf32x4*)(unsigned long long)(upo + 4 * (PWK_SLOT + q));
             const f32x4 va = *pa, vb = *pb;
-            const wf2 a0 = w_mul2(wf2{va[0], va[1]}, cs2A), a1 = w_mul2(wf2{va[2], va[3]}, cs2A);
-            const wf2 b0 = w_mul2(wf2{vb[0], vb[1]}, cs2B), b1 = w_mul2(wf2{vb[2], vb[3]}, cs2B);
+            const f32x2 a0 = w_mul2(f32x2{va[0], va[1]}, cs2A), a1 = w_mul2(f32x2{va[2], va[3]}, cs2A);
+            const f32x2 b0 = w_mul2(f32x2{vb[0], vb[1]}, cs2B), b1 = w_mul2(f32x2{vb[2], vb[3]}, cs2B);
             *pa = f32x4{a0[0], a0[1], a1[0], a1[1]};
             *pb = f32x4{b0[0], b0[1], b1[0], b1[1]};
         }
 
         f32x16 acc1A = zero16, acc2A = zero16, acc1B = zero16, acc2B = zero16;
         // pieces of h1 for one k step of one sub-step: relu(UP + UC) scaled into [0, 2^14], cut in two
-        auto cut = [&](const f32x4& a, const f32x4& c, const wf2 cs2, int ks, wu4& xh, wu4& xl) __attribute__((always_inline)) {
-            const wf2 upv[4] = {wf2{a[0], a[1]}, wf2{a[2], a[3]}, wf2{c[0], c[1]}, wf2{c[2], c[3]}};  // (scaled in place above)
+        auto cut = [&](const f32x4& a, const f32x4& c, const f32x2 cs2, int ks, u32x4& xh, u32x4& xl) __attribute__((always_inline)) {
+            const f32x2 upv[4] = {f32x2{a[0], a[1]}, f32x2{a[2], a[3]}, f32x2{c[0], c[1]}, f32x2{c[2], c[3]}};  // (scaled in place above)
 #pragma unroll
             for (int j2 = 0; j2 < 2; ++j2) {
                 const f32x4 uu = uc[ks][j2];
-                const wf2 sa = w_mul2(w_fma2_relu01(wf2{uu[0], uu[1]}, cs2, upv[2 * j2]), c14);
-                const wf2 sb = w_mul2(w_fma2_relu01(wf2{uu[2], uu[3]}, cs2, upv[2 * j2 + 1]), c14);
-                const uint32_t hA = w_cvt2(sa[0], sa[1]), hB = w_cvt2(sb[0], sb[1]);
+                const f32x2 sa = w_mul2(fma2_relu01(f32x2{uu[0], uu[1]}, cs2, upv[2 * j2]), c14);
+                const f32x2 sb = w_mul2(fma2_relu01(f32x2{uu[2], uu[3]}, cs2, upv[2 * j2 + 1]), c14);
+                const uint32_t hA = cvt_f16x2(sa[0], sa[1]), hB = cvt_f16x2(sb[0], sb[1]);
                 xh[2 * j2] = hA;
                 xh[2 * j2 + 1] = hB;
-                xl[2 * j2] = w_cvt2(w_res_lo(sa[0], hA), w_res_hi(sa[1], hA));
-                xl[2 * j2 + 1] = w_cvt2(w_res_lo(sb[0], hB), w_res_hi(sb[1], hB));
+                xl[2 * j2] = cvt_f16x2(f16_res_lo(sa[0], hA), f16_res_hi(sa[1], hA));
+                xl[2 * j2 + 1] = cvt_f16x2(f16_res_lo(sb[0], hB), f16_res_hi(sb[1], hB));
             }
         };
         // the LDS reads of k step ks + 1 (UP values of both tracks, weight pieces) are issued before the arithmetic of k step ks
         struct KIn {
             f32x4 a0, a1, b0, b1;
-            wu4 w1l, w1h, w2l, w2h;
+            u32x4 w1l, w1h, w2l, w2h;
         };
         auto fetch = [&](int ks, KIn& k) __attribute__((always_inline)) {
             k.a0 = *reinterpret_cast<const lf32x4*>(upA + 16 * ks + 8 * kb);
@@ -329,24 +290,24 @@ __global__ __launch_bounds__(64 * PWK_WPB) __attribute__((amdgpu_waves_per_eu(2,
         for (int ks = 0; ks < NKS; ++ks) {
             if (ks + 1 < NKS) fetch(ks + 1, kin[(ks + 1) & 1]);
             const KIn& k = kin[ks & 1];
-            wu4 xhA, xlA, xhB, xlB;
+            u32x4 xhA, xlA, xhB, xlB;
             cut(k.a0, k.a1, cs2A, ks, xhA, xlA);
             cut(k.b0, k.b1, cs2B, ks, xhB, xlB);
             if (W::has1(ks)) {  // (compile-time after the unrolling)
-                acc1A = MFMA32H(k.w1l, xhA, acc1A);
-                acc1B = MFMA32H(k.w1l, xhB, acc1B);
-                acc1A = MFMA32H(k.w1h, xlA, acc1A);
-                acc1B = MFMA32H(k.w1h, xlB, acc1B);
-                acc1A = MFMA32H(k.w1h, xhA, acc1A);
-                acc1B = MFMA32H(k.w1h, xhB, acc1B);
+                acc1A = mfma_32x32x16_f16(k.w1l, xhA, acc1A);
+                acc1B = mfma_32x32x16_f16(k.w1l, xhB, acc1B);
+                acc1A = mfma_32x32x16_f16(k.w1h, xlA, acc1A);
+                acc1B = mfma_32x32x16_f16(k.w1h, xlB, acc1B);
+                acc1A = mfma_32x32x16_f16(k.w1h, xhA, acc1A);
+                acc1B = mfma_32x32x16_f16(k.w1h, xhB, acc1B);
             }
             if (W::has2(ks)) {
-                acc2A = MFMA32H(k.w2l, xhA, acc2A);
-                acc2B = MFMA32H(k.w2l, xhB, acc2B);
-                acc2A = MFMA32H(k.w2h, xlA, acc2A);
-                acc2B = MFMA32H(k.w2h, xlB, acc2B);
-                acc2A = MFMA32H(k.w2h, xhA, acc2A);
-                acc2B = MFMA32H(k.w2h, xhB, acc2B);
+                acc2A = mfma_32x32x16_f16(k.w2l, xhA, acc2A);
+                acc2B = mfma_32x32x16_f16(k.w2l, xhB, acc2B);
+                acc2A = mfma_32x32x16_f16(k.w2h, xlA, acc2A);
+                acc2B = mfma_32x32x16_f16(k.w2h, xlB, acc2B);
+                acc2A = mfma_32x32x16_f16(k.w2h, xhA, acc2A);
+                acc2B = mfma_32x32x16_f16(k.w2h, xhB, acc2B);
             }
         }
         // ---- transposition: lanes 0..31 take pair (t, n), lanes 32..63 pair (t + 1, n) --------------------------------------
@@ -395,9 +356,9 @@ __global__ __launch_bounds__(64 * PWK_WPB) __attribute__((amdgpu_waves_per_eu(2,
             const float* b_fs = s_a4 + A4w<F, L_FS2>::OFF + A4w<F, L_FS2>::BIAS;
             const float* b_fd = s_a4 + A4w<F, L_FD2>::OFF + A4w<F, L_FD2>::BIAS;
             auto fma4 = [&](const f32x4& v, float sc, const f32x4& bb) __attribute__((always_inline)) {
-                const wf2 s2 = {sc, sc};
-                const wf2 lo = __builtin_elementwise_fma(wf2{v[0], v[1]}, s2, wf2{bb[0], bb[1]});
-                const wf2 hi = __builtin_elementwise_fma(wf2{v[2], v[3]}, s2, wf2{bb[2], bb[3]});
+                const f32x2 s2 = {sc, sc};
+                const f32x2 lo = __builtin_elementwise_fma(f32x2{v[0], v[1]}, s2, f32x2{bb[0], bb[1]});
+                const f32x2 hi = __builtin_elementwise_fma(f32x2{v[2], v[3]}, s2, f32x2{bb[2], bb[3]});
                 return f32x4{fmaxf(lo[0], 0.0f), fmaxf(lo[1], 0.0f), fmaxf(hi[0], 0.0f), fmaxf(hi[1], 0.0f)};
             };
 #pragma unroll

@@ -11,6 +11,9 @@
 // Later layers run with one LANE per pair on v_mfma_f32_4x4x1_16B_f32 (pair.hip): the four result registers of a lane are
 // four output features of its own pair, so a layer's accumulators are, unmoved, the next layer's inputs.
 #pragma once
+#if defined(__HIPCC__)
+#include "common.hpp"
+#endif
 
 namespace shasta {
 
@@ -122,6 +125,29 @@ struct PackedLayout {
 };
 
 #if defined(__HIPCC__)
+// Pack kernels of the fp16 pair kernels (pair_f16.hip, pair_f16w.hip), 256 threads: the range exponent of each of the three
+// second-layer matrices W[m] (cnt[m] floats; maxima by fmaxf), one per MLP.  On return every thread sees them in ex (LDS, like
+// red); they are also stored as ints at out[at + m], and out[at + 3] = 0.
+__device__ __forceinline__ void pair2_range_exponents(const float* const (&W)[3], const int (&cnt)[3], uint32_t* out, int at,
+                                                      float (&red)[3][4], int (&ex)[3]) {
+    const int tid = threadIdx.x;
+    for (int m = 0; m < 3; ++m) {
+        float mx = 0.0f;
+        for (int i = tid; i < cnt[m]; i += 256) mx = fmaxf(mx, fabsf(W[m][i]));
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+        if ((tid & 63) == 0) red[m][tid >> 6] = mx;
+    }
+    __syncthreads();
+    if (tid < 3) {
+        const float mx = fmaxf(fmaxf(red[tid][0], red[tid][1]), fmaxf(red[tid][2], red[tid][3]));
+        ex[tid] = range_exponent_bits(__float_as_uint(mx));
+        reinterpret_cast<int*>(out)[at + tid] = ex[tid];
+    }
+    if (tid == 3) out[at + 3] = 0;
+    __syncthreads();
+}
+
 // The hand-designed residual of one pair (det3d/models/tracker/shasta.py:277-283) from the hand rows of its track (hp, 16 floats)
 // and of its detection (hd: slots 0 - 6 and 8 - 12 of that row), the column norm dnm = max(||.||, 1e-12) of the detection and
 // rdn = 1.0f / dnm (IEEE, once per lane).  row_prep writes zeros into the box slots >= num_feats of both rows, so the sum of squares

@@ -24,17 +24,14 @@
 // Several class heads (the seven per-class models of tools/nusc_shasta, official_val.sh) run in ONE launch: blockIdx -> (tile, head)
 // with the heads of a tile next to each other on one XCD, so the map is read from HBM once and 6 of 7 tile reads hit that L2.
 #include "common.hpp"
+#include "lds_dma.hpp"
+#include "pieces.hpp"
 
 #include <string.h>
 
-#pragma clang diagnostic ignored "-Winline-asm"
 #include <type_traits>
 
 namespace shasta {
-
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t w32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int C16_TILE = 256;                  // pixels per workgroup
 constexpr int C16_NSLOT = 640;                 // padded pixel slots of one staged tile (W = 180 needs 626) incl. the 8 trash slots at the end
@@ -46,33 +43,8 @@ constexpr int C16_MAXH = 8;                    // class heads per launch
 constexpr int C16_PARAMS = 320;                // floats behind the fragments: alpha[64], beta'[64], bias[64], 2^-e[64], then [256] = 1.0 for a RAW head
                                                // (train mode: conv + bias as is, no BatchNorm, no ReLU - shared_conv_train.hip takes it from there)
 
-__device__ __forceinline__ void cut2(float a, _Float16& h, _Float16& l) {
-    h = (_Float16)a;
-    l = (_Float16)(a - (float)h);
-}
-// a pointer the compiler should keep in scalar registers (operands of the LDS-DMA asm)
-__device__ __forceinline__ const char* uniform_ptr(const char* p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return reinterpret_cast<const char*>(((uint64_t)hi << 32) | lo);
-}
-// x - h, exact in fp32, with h = the low / high half of a packed fp16 pair read as an fp16 operand (v_fma_mix_f32); the results go
-// through a compiler-generated conversion before anything else reads them (hazard rule of pair_f16.hip)
-typedef float c16f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float c16_res_lo(float x, uint32_t hpk) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(r) : "v"(x), "v"(hpk));
-    return r;
-}
-__device__ __forceinline__ float c16_res_hi(float x, uint32_t hpk) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r) : "v"(x), "v"(hpk));
-    return r;
-}
-__device__ __forceinline__ uint32_t pack2h(_Float16 even, _Float16 odd) {
-    const h16x2 v = {even, odd};
-    return __builtin_bit_cast(uint32_t, v);
-}
+// (the residuals f16_res_lo / f16_res_hi go through a compiler-generated conversion before anything else reads them: hazard rule of
+// pieces.hpp)
 
 // ---- pack: one workgroup per output channel --------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void conv16_pack_kernel(const float* __restrict__ w, const float* __restrict__ bias,
@@ -93,18 +65,18 @@ __global__ __launch_bounds__(256) void conv16_pack_kernel(const float* __restric
     const int nchunk = Cin / 16, nb = n >> 5, nl = n & 31;
     for (int it = tid; it < nchunk * 18; it += 256) {
         const int c = it / 18, r = it - c * 18, tap = r >> 1, h = r & 1;
-        w32x4 hi, lo;
+        u32x4 hi, lo;
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
             _Float16 h0, l0, h1, l1;
-            cut2(__builtin_ldexpf(wn[(16 * c + 8 * h + 2 * jj) * 9 + tap], e), h0, l0);
-            cut2(__builtin_ldexpf(wn[(16 * c + 8 * h + 2 * jj + 1) * 9 + tap], e), h1, l1);
-            hi[jj] = pack2h(h0, h1);
-            lo[jj] = pack2h(l0, l1);
+            cut2_f16(__builtin_ldexpf(wn[(16 * c + 8 * h + 2 * jj) * 9 + tap], e), h0, l0);
+            cut2_f16(__builtin_ldexpf(wn[(16 * c + 8 * h + 2 * jj + 1) * 9 + tap], e), h1, l1);
+            hi[jj] = pack_f16x2(h0, h1);
+            lo[jj] = pack_f16x2(l0, l1);
         }
         char* f = out + (size_t)c * C16_WBUF + ((tap * 2 + nb) * 2) * 1024 + (h * 32 + nl) * 16;
-        *reinterpret_cast<w32x4*>(f) = hi;
-        *reinterpret_cast<w32x4*>(f + 1024) = lo;
+        *reinterpret_cast<u32x4*>(f) = hi;
+        *reinterpret_cast<u32x4*>(f + 1024) = lo;
     }
     if (tid == 0) {
         float* par = reinterpret_cast<float*>(out + (size_t)nchunk * C16_WBUF);
@@ -180,8 +152,8 @@ __global__ __launch_bounds__(512 / PB, PB == 1 ? 2 : 1) void shared_conv_f16_ker
 
     // zero both input buffers once: padding slots and rows outside the image are never written afterwards
     {
-        const w32x4 zz = {0u, 0u, 0u, 0u};
-        for (int i = tid; i < 2 * C16_INBUF / 16; i += 64 * NW) reinterpret_cast<w32x4*>(in_lds)[i] = zz;
+        const u32x4 zz = {0u, 0u, 0u, 0u};
+        for (int i = tid; i < 2 * C16_INBUF / 16; i += 64 * NW) reinterpret_cast<u32x4*>(in_lds)[i] = zz;
     }
 
     // staging roles of this lane: three (pixel, channel octet) items of every chunk.  The flat pixel range the tile touches is dealt in
@@ -208,7 +180,7 @@ __global__ __launch_bounds__(512 / PB, PB == 1 ? 2 : 1) void shared_conv_f16_ker
         ld_off[it] = 4u * (unsigned)(oct * 8 * npix + (ok ? q : 0));
     }
     const float scale = __builtin_ldexpf(1.0f, eimg);
-    const c16f2 scale2 = {scale, scale};
+    const f32x2 scale2 = {scale, scale};
 
     // The raw tile travels in registers for a whole trip.  Its loads are inline asm: hipcc builds a 64-bit vector address per load
     // otherwise (24 v_lshl_add_u64 per trip - vector instructions of a wave take issue slots from its SIMD partner's matrix
@@ -246,7 +218,7 @@ __global__ __launch_bounds__(512 / PB, PB == 1 ? 2 : 1) void shared_conv_f16_ker
         for (int j = 0; j < decltype(ndma)::value; ++j) {
             const char* base = uniform_ptr(src + j * (NW * 1024));
             const uint32_t dst = __builtin_amdgcn_readfirstlane(dst0 + (uint32_t)(j * (NW * 1024)));
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(dst) : "memory", "m0");
+            lds_dma_x4(off, base, dst);
         }
     };
     auto cut_store = [&](auto bufc) __attribute__((always_inline)) {
@@ -254,16 +226,16 @@ __global__ __launch_bounds__(512 / PB, PB == 1 ? 2 : 1) void shared_conv_f16_ker
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             if (!item_live[it]) continue;  // wave-uniform
-            w32x4 hi, lo;
+            u32x4 hi, lo;
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj) {  // 2.5 vector instructions per value: packed scale, packed convert, two exact residuals, packed convert
-                const c16f2 sv = c16f2{r[it][2 * jj], r[it][2 * jj + 1]} * scale2;
-                const uint32_t hp = pack2h((_Float16)sv[0], (_Float16)sv[1]);
+                const f32x2 sv = f32x2{r[it][2 * jj], r[it][2 * jj + 1]} * scale2;
+                const uint32_t hp = pack_f16x2((_Float16)sv[0], (_Float16)sv[1]);
                 hi[jj] = hp;
-                lo[jj] = pack2h((_Float16)c16_res_lo(sv[0], hp), (_Float16)c16_res_hi(sv[1], hp));
+                lo[jj] = pack_f16x2((_Float16)f16_res_lo(sv[0], hp), (_Float16)f16_res_hi(sv[1], hp));
             }
-            *reinterpret_cast<w32x4*>(lds + IB + st_addr[it]) = hi;
-            *reinterpret_cast<w32x4*>(lds + IB + 2 * C16_PLANE + st_addr[it]) = lo;
+            *reinterpret_cast<u32x4*>(lds + IB + st_addr[it]) = hi;
+            *reinterpret_cast<u32x4*>(lds + IB + 2 * C16_PLANE + st_addr[it]) = lo;
         }
     };
 
@@ -285,7 +257,7 @@ __global__ __launch_bounds__(512 / PB, PB == 1 ? 2 : 1) void shared_conv_f16_ker
 #pragma unroll
     for (int pb = 0; pb < PB; ++pb) acc[pb][0] = acc[pb][1] = zero16;
     struct Frag {
-        h16x8 ah[PB], al[PB], b0h, b0l, b1h, b1l;
+        f16x8 ah[PB], al[PB], b0h, b0l, b1h, b1l;
     };
     auto read_tap = [&](auto bufc, int tap, Frag& f) __attribute__((always_inline)) {
         const char* ib = in_lds + decltype(bufc)::value * C16_INBUF;
@@ -293,13 +265,13 @@ __global__ __launch_bounds__(512 / PB, PB == 1 ? 2 : 1) void shared_conv_f16_ker
         const int dy = tap / 3, dx = tap % 3;
 #pragma unroll
         for (int pb = 0; pb < PB; ++pb) {
-            f.ah[pb] = *reinterpret_cast<const h16x8*>(ib + a_row[pb][dy] + dx * 16);
-            f.al[pb] = *reinterpret_cast<const h16x8*>(ib + a_row[pb][dy] + dx * 16 + 2 * C16_PLANE);
+            f.ah[pb] = *reinterpret_cast<const f16x8*>(ib + a_row[pb][dy] + dx * 16);
+            f.al[pb] = *reinterpret_cast<const f16x8*>(ib + a_row[pb][dy] + dx * 16 + 2 * C16_PLANE);
         }
-        f.b0h = *reinterpret_cast<const h16x8*>(wb + (tap * 4 + 0) * 1024);
-        f.b0l = *reinterpret_cast<const h16x8*>(wb + (tap * 4 + 1) * 1024);
-        f.b1h = *reinterpret_cast<const h16x8*>(wb + (tap * 4 + 2) * 1024);
-        f.b1l = *reinterpret_cast<const h16x8*>(wb + (tap * 4 + 3) * 1024);
+        f.b0h = *reinterpret_cast<const f16x8*>(wb + (tap * 4 + 0) * 1024);
+        f.b0l = *reinterpret_cast<const f16x8*>(wb + (tap * 4 + 1) * 1024);
+        f.b1h = *reinterpret_cast<const f16x8*>(wb + (tap * 4 + 2) * 1024);
+        f.b1l = *reinterpret_cast<const f16x8*>(wb + (tap * 4 + 3) * 1024);
     };
     auto mma_tap = [&](const Frag& f) __attribute__((always_inline)) {  // piece products, small to large
 #pragma unroll
@@ -460,8 +432,8 @@ __global__ __launch_bounds__(512, 2) void shared_conv_f16w_kernel(Conv16Args a) 
     const int first = (y0 - 1) * WT + x0;  // padded index (y * WT + x + 1) of pixel (y0 - 1, x0 - 1) = slot 0
     char* const in_lds = lds + C16_WBUF;
     {   // zero both input buffers once: padding slots and rows outside the image are never written afterwards
-        const w32x4 zz = {0u, 0u, 0u, 0u};
-        for (int i = tid; i < 2 * W2_INBUF / 16; i += 64 * NW) reinterpret_cast<w32x4*>(in_lds)[i] = zz;
+        const u32x4 zz = {0u, 0u, 0u, 0u};
+        for (int i = tid; i < 2 * W2_INBUF / 16; i += 64 * NW) reinterpret_cast<u32x4*>(in_lds)[i] = zz;
     }
     // staging roles of this lane (as above): block 8 i + w of the 64-pixel blocks (first all of octet 0, then those of octet 1) is item i of wave w
     const int p_last = min(p0 + W2_TILE, npix) - 1;
@@ -483,7 +455,7 @@ __global__ __launch_bounds__(512, 2) void shared_conv_f16w_kernel(Conv16Args a) 
         ld_off[it] = 4u * (unsigned)(oct * 8 * npix + (ok ? q : 0));
     }
     const float scale = __builtin_ldexpf(1.0f, eimg);
-    const c16f2 scale2 = {scale, scale};
+    const f32x2 scale2 = {scale, scale};
     float r[NIT][8];
     auto load_chunk = [&](int ch) __attribute__((always_inline)) {
         const char* xc = reinterpret_cast<const char*>(xin + (size_t)ch * 16 * npix);
@@ -514,7 +486,7 @@ __global__ __launch_bounds__(512, 2) void shared_conv_f16w_kernel(Conv16Args a) 
         for (int j = 0; j < CNT; ++j) {
             const char* base = uniform_ptr(src + j * (NW * 1024));
             const uint32_t dst = __builtin_amdgcn_readfirstlane(dst0 + (uint32_t)(j * (NW * 1024)));
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(dst) : "memory", "m0");
+            lds_dma_x4(off, base, dst);
         }
     };
     auto cut_store = [&](auto bufc) __attribute__((always_inline)) {
@@ -522,16 +494,16 @@ __global__ __launch_bounds__(512, 2) void shared_conv_f16w_kernel(Conv16Args a) 
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             if (!item_live[it]) continue;  // wave-uniform
-            w32x4 hi, lo;
+            u32x4 hi, lo;
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj) {
-                const c16f2 sv = c16f2{r[it][2 * jj], r[it][2 * jj + 1]} * scale2;
-                const uint32_t hp = pack2h((_Float16)sv[0], (_Float16)sv[1]);
+                const f32x2 sv = f32x2{r[it][2 * jj], r[it][2 * jj + 1]} * scale2;
+                const uint32_t hp = pack_f16x2((_Float16)sv[0], (_Float16)sv[1]);
                 hi[jj] = hp;
-                lo[jj] = pack2h((_Float16)c16_res_lo(sv[0], hp), (_Float16)c16_res_hi(sv[1], hp));
+                lo[jj] = pack_f16x2((_Float16)f16_res_lo(sv[0], hp), (_Float16)f16_res_hi(sv[1], hp));
             }
-            *reinterpret_cast<w32x4*>(lds + IB + st_addr[it]) = hi;
-            *reinterpret_cast<w32x4*>(lds + IB + 2 * W2_PLANE + st_addr[it]) = lo;
+            *reinterpret_cast<u32x4*>(lds + IB + st_addr[it]) = hi;
+            *reinterpret_cast<u32x4*>(lds + IB + 2 * W2_PLANE + st_addr[it]) = lo;
         }
     };
     // operand addresses of this lane: pixel block pb of this wave = pixels 64 w + 32 pb + (lane & 31)
@@ -551,7 +523,7 @@ __global__ __launch_bounds__(512, 2) void shared_conv_f16w_kernel(Conv16Args a) 
 #pragma unroll
     for (int pb = 0; pb < PB; ++pb) acc[pb][0] = acc[pb][1] = zero16;
     struct Frag {
-        h16x8 ah[PB], al[PB], b0h, b0l, b1h, b1l;
+        f16x8 ah[PB], al[PB], b0h, b0l, b1h, b1l;
     };
     auto read_tap = [&](auto bufc, int tap, Frag& f) __attribute__((always_inline)) {
         const char* ib = in_lds + decltype(bufc)::value * W2_INBUF;
@@ -559,13 +531,13 @@ __global__ __launch_bounds__(512, 2) void shared_conv_f16w_kernel(Conv16Args a) 
         const int dy = tap / 3, dx = tap % 3;
 #pragma unroll
         for (int pb = 0; pb < PB; ++pb) {
-            f.ah[pb] = *reinterpret_cast<const h16x8*>(ib + a_row[pb][dy] + dx * 16);
-            f.al[pb] = *reinterpret_cast<const h16x8*>(ib + a_row[pb][dy] + dx * 16 + 2 * W2_PLANE);
+            f.ah[pb] = *reinterpret_cast<const f16x8*>(ib + a_row[pb][dy] + dx * 16);
+            f.al[pb] = *reinterpret_cast<const f16x8*>(ib + a_row[pb][dy] + dx * 16 + 2 * W2_PLANE);
         }
-        f.b0h = *reinterpret_cast<const h16x8*>(wb + (tap * 4 + 0) * 1024);
-        f.b0l = *reinterpret_cast<const h16x8*>(wb + (tap * 4 + 1) * 1024);
-        f.b1h = *reinterpret_cast<const h16x8*>(wb + (tap * 4 + 2) * 1024);
-        f.b1l = *reinterpret_cast<const h16x8*>(wb + (tap * 4 + 3) * 1024);
+        f.b0h = *reinterpret_cast<const f16x8*>(wb + (tap * 4 + 0) * 1024);
+        f.b0l = *reinterpret_cast<const f16x8*>(wb + (tap * 4 + 1) * 1024);
+        f.b1h = *reinterpret_cast<const f16x8*>(wb + (tap * 4 + 2) * 1024);
+        f.b1l = *reinterpret_cast<const f16x8*>(wb + (tap * 4 + 3) * 1024);
     };
     auto mma_tap = [&](const Frag& f) __attribute__((always_inline)) {  // piece products, small to large
 #pragma unroll
@@ -701,7 +673,7 @@ static inline long conv16p_plane_slots(int H, int W) { return ((long)(H + 2) * (
 
 // grid (ceil(plane slots / 256), 2 chunks-octets ..., maps): thread = (padded slot, octet) of one chunk
 __global__ __launch_bounds__(256) void conv16_precut_kernel(const float* __restrict__ xa, const float* __restrict__ xb, int B, int Cin, int H, int W,
-                                                            const unsigned* __restrict__ xmax, w32x4* __restrict__ img, long plane_slots) {
+                                                            const unsigned* __restrict__ xmax, u32x4* __restrict__ img, long plane_slots) {
     const int z = blockIdx.z, co = blockIdx.y, ch = co >> 1, oct = co & 1;
     const long s = (long)blockIdx.x * 256 + threadIdx.x;
     if (s >= plane_slots) return;
@@ -709,19 +681,19 @@ __global__ __launch_bounds__(256) void conv16_precut_kernel(const float* __restr
     const long row = s / WT;
     const int xp = (int)(s - row * WT);
     const bool real = row >= 1 && row <= H && xp >= 1 && xp <= W;
-    w32x4 hi = {0u, 0u, 0u, 0u}, lo = {0u, 0u, 0u, 0u};
+    u32x4 hi = {0u, 0u, 0u, 0u}, lo = {0u, 0u, 0u, 0u};
     if (real) {
         const float* x = (z >= B ? xb + (size_t)(z - B) * Cin * npix : xa + (size_t)z * Cin * npix) + (size_t)(16 * ch + 8 * oct) * npix + (row - 1) * W + (xp - 1);
         const float scale = __builtin_ldexpf(1.0f, range_exponent_bits(xmax[z]));
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
             const float v0 = x[(size_t)(2 * jj) * npix] * scale, v1 = x[(size_t)(2 * jj + 1) * npix] * scale;
-            const uint32_t hp = pack2h((_Float16)v0, (_Float16)v1);
+            const uint32_t hp = pack_f16x2((_Float16)v0, (_Float16)v1);
             hi[jj] = hp;
-            lo[jj] = pack2h((_Float16)c16_res_lo(v0, hp), (_Float16)c16_res_hi(v1, hp));
+            lo[jj] = pack_f16x2((_Float16)f16_res_lo(v0, hp), (_Float16)f16_res_hi(v1, hp));
         }
     }
-    w32x4* o = img + (((size_t)z * (Cin / 16) + ch) * 4 + oct) * plane_slots + s;
+    u32x4* o = img + (((size_t)z * (Cin / 16) + ch) * 4 + oct) * plane_slots + s;
     o[0] = hi;
     o[2 * plane_slots] = lo;
 }
@@ -768,7 +740,7 @@ __global__ __launch_bounds__(512, 2) void shared_conv_f16p_kernel(Conv16pArgs pa
         for (int j = 0; j < CNT; ++j) {
             const char* base = uniform_ptr(src + j * (NW * 1024));
             const uint32_t dst = __builtin_amdgcn_readfirstlane(dst0 + (uint32_t)(j * (NW * 1024)));
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(dst) : "memory", "m0");
+            lds_dma_x4(off, base, dst);
         }
     };
     // the tile of chunk ch into input buffer `buf`: 4 planes x 14 KB = 56 instructions of 1 KB, seven per wave (instruction 8 j + w)
@@ -779,7 +751,7 @@ __global__ __launch_bounds__(512, 2) void shared_conv_f16p_kernel(Conv16pArgs pa
             const int i = 8 * j + wv, pl = i / 14, k = i - pl * 14;  // plane (piece * 2 + octet), KB within it
             const char* base = uniform_ptr(tsrc + ((size_t)ch * 4 + pl) * plane_bytes + (size_t)k * 1024);
             const uint32_t dst = __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(C16_WBUF + buf * P3_INBUF + pl * P3_PLANE + k * 1024));
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(dst) : "memory", "m0");
+            lds_dma_x4(off, base, dst);
         }
     };
     const int li = lane & 31, h = lane >> 5;
@@ -798,7 +770,7 @@ __global__ __launch_bounds__(512, 2) void shared_conv_f16p_kernel(Conv16pArgs pa
 #pragma unroll
     for (int pb = 0; pb < PB; ++pb) acc[pb][0] = acc[pb][1] = zero16;
     struct Frag {
-        h16x8 ah[PB], al[PB], b0h, b0l, b1h, b1l;
+        f16x8 ah[PB], al[PB], b0h, b0l, b1h, b1l;
     };
     auto read_tap = [&](auto bufc, int tap, Frag& f) __attribute__((always_inline)) {
         const char* ib = in_lds + decltype(bufc)::value * P3_INBUF;
@@ -806,13 +778,13 @@ __global__ __launch_bounds__(512, 2) void shared_conv_f16p_kernel(Conv16pArgs pa
         const int dy = tap / 3, dx = tap % 3;
 #pragma unroll
         for (int pb = 0; pb < PB; ++pb) {
-            f.ah[pb] = *reinterpret_cast<const h16x8*>(ib + a_row[pb][dy] + dx * 16);
-            f.al[pb] = *reinterpret_cast<const h16x8*>(ib + a_row[pb][dy] + dx * 16 + 2 * P3_PLANE);
+            f.ah[pb] = *reinterpret_cast<const f16x8*>(ib + a_row[pb][dy] + dx * 16);
+            f.al[pb] = *reinterpret_cast<const f16x8*>(ib + a_row[pb][dy] + dx * 16 + 2 * P3_PLANE);
         }
-        f.b0h = *reinterpret_cast<const h16x8*>(wb + (tap * 4 + 0) * 1024);
-        f.b0l = *reinterpret_cast<const h16x8*>(wb + (tap * 4 + 1) * 1024);
-        f.b1h = *reinterpret_cast<const h16x8*>(wb + (tap * 4 + 2) * 1024);
-        f.b1l = *reinterpret_cast<const h16x8*>(wb + (tap * 4 + 3) * 1024);
+        f.b0h = *reinterpret_cast<const f16x8*>(wb + (tap * 4 + 0) * 1024);
+        f.b0l = *reinterpret_cast<const f16x8*>(wb + (tap * 4 + 1) * 1024);
+        f.b1h = *reinterpret_cast<const f16x8*>(wb + (tap * 4 + 2) * 1024);
+        f.b1l = *reinterpret_cast<const f16x8*>(wb + (tap * 4 + 3) * 1024);
     };
     auto mma_tap = [&](const Frag& f) __attribute__((always_inline)) {  // piece products, small to large
 #pragma unroll
@@ -1071,7 +1043,7 @@ static int conv_multi(const float* x, const float* x_prev, int B, int in_channel
         char* img = static_cast<char*>(workspace) + shasta_shared_conv_multi_workspace_bytes(B);
         pa.img = img;
         hipLaunchKernelGGL(conv16_precut_kernel, dim3((unsigned)cdiv((int)pa.plane_slots, 256), 2 * (in_channels / 16), nmaps), dim3(256), 0, st, x, x_prev, B,
-                           in_channels, H, W, xmax, reinterpret_cast<w32x4*>(img), pa.plane_slots);
+                           in_channels, H, W, xmax, reinterpret_cast<u32x4*>(img), pa.plane_slots);
         if ((rc = check_launch("shared_conv_multi (piece image)")) != SHASTA_OK) return rc;
         a.tiles_per_map = cdiv(H * W, W2_TILE);
         a.ntiles = a.tiles_per_map * nmaps;

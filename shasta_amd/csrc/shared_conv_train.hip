@@ -27,26 +27,14 @@
 //    this split's partial; conv_wgrad_reduce_kernel adds the splits in order.
 //  * workgroups that read the same dy rows (the 16 channel blocks of a split) are neighbours on one XCD: dy crosses HBM once.
 #include "common.hpp"
+#include "pieces.hpp"
 
 #include <string.h>
 
 namespace shasta {
 
-typedef _Float16 t16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 t16x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int BN_C = 64;          // channels of shared_conv
 constexpr int BN_SLICES = 1024;   // workgroups (and partials) of a reduction pass at most
-
-__device__ __forceinline__ uint32_t tr_pack2h(_Float16 even, _Float16 odd) {
-    const t16x2 v = {even, odd};
-    return __builtin_bit_cast(uint32_t, v);
-}
-__device__ __forceinline__ void tr_cut2(float a, _Float16& h, _Float16& l) {
-    h = (_Float16)a;
-    l = (_Float16)(a - (float)h);
-}
 
 // ---- batch statistics of y (M, 64): per channel sum and sum of squares in float64 (products of fp32 values are exact in float64),
 // partials per workgroup, combined in order; out: mean[64], M2[64] = sum of squared deviations from that mean ------------------------
@@ -292,10 +280,10 @@ __global__ __launch_bounds__(256) void bn_bwd_dy_kernel(const float* __restrict_
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
             _Float16 h0, l0, h1, l1;
-            tr_cut2(src[(2 * jj) * 65], h0, l0);
-            tr_cut2(src[(2 * jj + 1) * 65], h1, l1);
-            hi[jj] = tr_pack2h(h0, h1);
-            lo[jj] = tr_pack2h(l0, l1);
+            cut2_f16(src[(2 * jj) * 65], h0, l0);
+            cut2_f16(src[(2 * jj + 1) * 65], h1, l1);
+            hi[jj] = pack_f16x2(h0, h1);
+            lo[jj] = pack_f16x2(l0, l1);
         }
         char* f = out + ((size_t)(k * 2 + ob) * 2) * 1024 + lane * 16;
         *reinterpret_cast<u32x4*>(f) = hi;
@@ -376,10 +364,10 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_kernel(WgradArgs a) {
             const int p = 2 * (sl + 16 * i);
             if (p < W) {  // (the odd column beyond an odd W holds a zero: it is a padding column)
                 _Float16 h0, l0, h1, l1;
-                tr_cut2(sv[i][0] * xscale, h0, l0);
-                tr_cut2(sv[i][1] * xscale, h1, l1);
-                *reinterpret_cast<uint32_t*>(dst + 2 * p) = tr_pack2h(h0, h1);
-                *reinterpret_cast<uint32_t*>(dst + PIECE + 2 * p) = tr_pack2h(l0, l1);
+                cut2_f16(sv[i][0] * xscale, h0, l0);
+                cut2_f16(sv[i][1] * xscale, h1, l1);
+                *reinterpret_cast<uint32_t*>(dst + 2 * p) = pack_f16x2(h0, h1);
+                *reinterpret_cast<uint32_t*>(dst + PIECE + 2 * p) = pack_f16x2(l0, l1);
             }
         }
     };
@@ -397,11 +385,11 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_kernel(WgradArgs a) {
     const char* fragz = a.frag + (size_t)z * H * KS * 4096 + (size_t)ob * 2048 + lane * 16;
     // the dy fragments of a k-step stay in registers for its nine taps; those of the NEXT row's k-step are requested into the same
     // registers as soon as the step is done, and have the rest of the row to arrive
-    t16x8 ah[MAXKQ], al[MAXKQ];
+    f16x8 ah[MAXKQ], al[MAXKQ];
     auto load_a = [&](int row, int i) __attribute__((always_inline)) {
         const char* f = fragz + ((size_t)row * KS + (kq + 4 * i)) * 4096;
-        ah[i] = *reinterpret_cast<const t16x8*>(f);
-        al[i] = *reinterpret_cast<const t16x8*>(f + 1024);
+        ah[i] = *reinterpret_cast<const f16x8*>(f);
+        al[i] = *reinterpret_cast<const f16x8*>(f + 1024);
     };
 #pragma unroll
     for (int i = 0; i < MAXKQ; ++i) load_a(r0, i);
@@ -418,7 +406,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_kernel(WgradArgs a) {
 #pragma unroll
             for (int ky = 0; ky < 3; ++ky) {
                 const char* rowp = lds + ((r + ky) & 3) * SLOT + b_lane + 32 * k;  // row r + ky - 1 sits in slot (row + 1) & 3
-                t16x8 bh[3], bl[3];
+                f16x8 bh[3], bl[3];
 #pragma unroll
                 for (int pc = 0; pc < 2; ++pc) {
                     const char* q = rowp + pc * PIECE;
@@ -428,10 +416,10 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_kernel(WgradArgs a) {
                                         __builtin_amdgcn_alignbit(w[2], w[1], 16), __builtin_amdgcn_alignbit(w[3], w[2], 16)};
                     const u32x4 right = {__builtin_amdgcn_alignbit(w[1], w[0], 16), __builtin_amdgcn_alignbit(w[2], w[1], 16),
                                          __builtin_amdgcn_alignbit(w[3], w[2], 16), __builtin_amdgcn_alignbit(wp, w[3], 16)};
-                    t16x8* d = pc ? bl : bh;
-                    d[0] = __builtin_bit_cast(t16x8, left);    // kx = 0: columns shifted by -1
-                    d[1] = __builtin_bit_cast(t16x8, w);
-                    d[2] = __builtin_bit_cast(t16x8, right);   // kx = 2: columns shifted by +1
+                    f16x8* d = pc ? bl : bh;
+                    d[0] = __builtin_bit_cast(f16x8, left);    // kx = 0: columns shifted by -1
+                    d[1] = __builtin_bit_cast(f16x8, w);
+                    d[2] = __builtin_bit_cast(f16x8, right);   // kx = 2: columns shifted by +1
                 }
                 // piece products small to large, the three taps of the row interleaved (a tap's accumulator is touched every third MFMA)
 #pragma unroll
