@@ -139,13 +139,25 @@ def bev_gather(bev_nhwc, boxes7, num_point, pc_start=(-54.0, -54.0), voxel_size=
 # --------------------------------------------------------------------------------------
 # generic Sequential(Linear, ReLU, Linear, ...) evaluation from the weight dict
 # --------------------------------------------------------------------------------------
-def _mlp(w, prefix, x):
+# Tests of the training path look at (or shift) the argument of every kink of the forward: when set,
+# KINK_HOOK(key, x, cols, kind) is called with the output x of layer `key` ("aff.4", "aug_dets.0.2", ...) right before the ReLU
+# (kind "relu") - or the abs() of the anchor heads (kind "abs") - that follows it, `cols` = the slice of the last axis the kink
+# applies to, and its return value takes the place of x.
+KINK_HOOK = None
+
+
+def _mlp(w, prefix, x, abs_cols=None):
+    """abs_cols: the caller applies abs() to these columns of the last layer's output (a kink like the ReLUs, see KINK_HOOK)."""
     idx = sorted({int(k[len(prefix) + 1:].split(".")[0]) for k in w if k.startswith(prefix + ".")
                   and k.endswith(".weight")})
     for j, i in enumerate(idx):
         x = TF.linear(x, w[f"{prefix}.{i}.weight"], w[f"{prefix}.{i}.bias"])
         if j + 1 < len(idx):
+            if KINK_HOOK is not None:
+                x = KINK_HOOK(f"{prefix}.{i}", x, slice(None), "relu")
             x = torch.relu(x)
+        elif abs_cols is not None and KINK_HOOK is not None:
+            x = KINK_HOOK(f"{prefix}.{i}", x, abs_cols, "abs")
     return x
 
 
@@ -165,7 +177,7 @@ def shared_conv_nhwc(w, bev_nchw, bn_eps=1e-5, batch_stats=False):
 def anchor_shape(w, i, table):
     """table (B,N,F) -> (B,1,F): abs(MLP(flattened table))."""
     B = table.shape[0]
-    return torch.abs(_mlp(w, f"aug_shape.{i}", table.reshape(B, -1))).reshape(B, 1, -1)
+    return torch.abs(_mlp(w, f"aug_shape.{i}", table.reshape(B, -1), abs_cols=slice(None))).reshape(B, 1, -1)
 
 
 def anchor_box(w, i, boxes7):
@@ -173,7 +185,7 @@ def anchor_box(w, i, boxes7):
     B = boxes7.shape[0]
     # (.clone(): at max_obj = 1 the reshape is a VIEW of the box table, which the back-projection then writes in place - autograd
     # refuses the saved input; for every other size the reshape copies anyway)
-    a = _mlp(w, f"aug_dets.{i}", boxes7.reshape(B, -1).clone()).reshape(B, 1, 7)
+    a = _mlp(w, f"aug_dets.{i}", boxes7.reshape(B, -1).clone(), abs_cols=slice(3, 6)).reshape(B, 1, 7)
     return torch.cat([a[:, :, :3], torch.abs(a[:, :, 3:6]), a[:, :, 6:]], dim=-1)
 
 
@@ -227,7 +239,7 @@ def affinity(w, residual):
 # --------------------------------------------------------------------------------------
 def forward_from_bev(w, bev_nhwc, prev_bev_nhwc, det_boxes, prev_det_boxes, num_feats, num_point,
                      pc_start=(-54.0, -54.0), voxel_size=(0.075, 0.075), out_stride=8,
-                     return_intermediates=False, grad=False):
+                     return_intermediates=False, grad=False, pair_chunk=64):
     """det_boxes / prev_det_boxes: (B,N,11) fp32.  det_boxes[:,:,:2] is back-projected IN PLACE,
     like the reference does to example["det_boxes"] (shasta.py:216,270).
     Returns (matched1 (B,N,N+2), matched2 (B,N+2,N)[, intermediates]).  grad=True keeps the autograd graph
@@ -249,7 +261,7 @@ def forward_from_bev(w, bev_nhwc, prev_bev_nhwc, det_boxes, prev_det_boxes, num_
         det7[:, :, :2] = det7[:, :, :2] - vel * dt
         prev_a = torch.cat([prev7, newborn, fp], dim=1)
         det_a = torch.cat([det7, dead, fn], dim=1)
-        residual = pair_residual(w, pfeat_a, feat_a, prev_a, det_a, num_feats)
+        residual = pair_residual(w, pfeat_a, feat_a, prev_a, det_a, num_feats, chunk=pair_chunk)
         matched, m1, m2 = affinity(w, residual)
     if return_intermediates:
         return m1, m2, dict(feature=feat, prev_feature=pfeat, newborn_geom=newborn_g, fp_geom=fp_g,

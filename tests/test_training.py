@@ -320,7 +320,11 @@ _PAIR_MLP_WIDTHS = {  # (kind, F) -> layer widths behind the factorised first la
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind,F,B,T,D", [(0, 64, 2, 5, 7), (2, 64, 1, 22, 22), (1, 64, 3, 66, 65), (0, 256, 2, 92, 92), (2, 256, 1, 130, 70),
                                           (1, 256, 2, 9, 200), (0, 320, 1, 33, 129), (2, 320, 2, 92, 92), (2, 256, 3, 1, 1), (2, 256, 1, 602, 602), (0, 320, 1, 700, 333),
-                                          (1, 64, 40, 17, 65)])
+                                          (1, 64, 40, 17, 65)] +
+                         # the seams of the 64-detection tiles, the per-wave track slices and the 256 / E1-row chunks, from both sides; at
+                         # B = 40 another plan of workgroups (one workgroup row, longer slices)
+                         [(kind, F, 1, T, D) for kind, F in ((2, 256), (0, 320)) for T, D in ((63, 65), (64, 64), (65, 63), (127, 129), (129, 127), (257, 255))] +
+                         [(kind, F, 40, T, D) for kind, F in ((2, 256), (0, 320)) for T, D in ((65, 63), (129, 127))])
 def test_pair_mlp_on_chip_matches_autograd(kind, F, B, T, D):
     """csrc/pair_bwd.hip: a pair MLP behind its factorised first layer, forward and backward per pair on chip, against torch autograd of
     the dense formulation in float64: the output, the gradients of both first-layer tables (sums over the detections / the tracks) and
