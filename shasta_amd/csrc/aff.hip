@@ -5,7 +5,7 @@
 // The six layers are six launches of the generic matrix-core GEMM over the B*T rows (bias + ReLU fused).
 #include <algorithm>
 
-#include "common.hpp"
+#include "stages.hpp"
 #include "pair_layout.hpp"
 
 namespace shasta {
@@ -262,23 +262,6 @@ __global__ __launch_bounds__(64 * AFF_WAVES) void aff_fused_kernel(AffArgs a) {
     }
 }
 
-size_t aff_frame_workspace_bytes(int B, int N);
-static size_t aff_matched_bytes(int B, int N) {
-    const int T = N + 2, Dp = (T + 3) / 4 * 4;
-    return align_up((size_t)B * T * Dp * sizeof(float), 256);
-}
-// matched (B, T, Dp) between the row MLP and the column softmax (two-kernel forms), then the column partials and arrival counters of
-// the one-pass form
-size_t aff_workspace_bytes(int B, int N) { return aff_matched_bytes(B, N) + aff_frame_workspace_bytes(B, N); }
-
-bool aff_pieces_serves(int D);
-int launch_aff_frame16(const shasta_weights* w, const float* packed16, const float* residual, int ld, float* matched, int ldm, float* m1,
-                       float* m2, int B, void* ws, hipStream_t st);
-int launch_aff_frame(const shasta_weights* w, const float* packed_pieces, const float* residual, int ld, float* matched, int ldm, float* m1,
-                     float* m2, int B, void* ws, hipStream_t st);
-int launch_aff_pieces(const shasta_weights* w, const float* packed_pieces, const float* residual, int ld, float* matched, int ldm,
-                      float* m1, int M, hipStream_t st);
-
 // the piece forms of the six layers serve this call (and, unless SHASTA_OPT_TWO_PASS_AFF, the one-pass kernel with its sibling wait)
 static bool aff_piece_form(const shasta_weights* w, int B, int ld, const void* residual, const void* ws) {
     const int M = B * (w->max_obj + 2);
@@ -286,14 +269,14 @@ static bool aff_piece_form(const shasta_weights* w, int B, int ld, const void* r
            (uintptr_t)residual % 16 == 0 && (uintptr_t)ws % 16 == 0;
 }
 
-// Status word of the most recent aff launch on workspace `ws` (aff_workspace_bytes): 0, or bit 0 = a row group's wait for its siblings
+// Status word of the most recent aff launch on workspace `ws` (AffWs): 0, or bit 0 = a row group's wait for its siblings
 // timed out (those rows of matched2 are NaN).  Only the one-pass form has something to report; the other forms give 0.  Synchronises
 // on the stream.  `ld`: the residual's leading dimension of that launch.
 int aff_status(const shasta_weights* w, int B, int ld, const void* ws, int* status, hipStream_t st) {
     *status = 0;
     if (B == 0 || !aff_piece_form(w, B, ld, nullptr, ws) || (w->options & SHASTA_OPT_TWO_PASS_AFF)) return SHASTA_OK;
     unsigned word = 0;
-    const char* src = static_cast<const char*>(ws) + aff_matched_bytes(B, w->max_obj);
+    const char* src = static_cast<const char*>(ws) + AffWs(B, w->max_obj).ctrl;
     hipError_t e = hipMemcpyAsync(&word, src, sizeof(word), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
@@ -306,15 +289,16 @@ int aff_status(const shasta_weights* w, int B, int ld, const void* ws, int* stat
 
 int aff_softmax(const shasta_weights* w, const float* packed, int B, const float* residual, int ld, float* m1,
                 float* m2, float* matched_out, void* ws, size_t ws_bytes, hipStream_t st) {
-    const int N = w->max_obj, T = N + 2, D = N + 2, Dp = (T + 3) / 4 * 4;
+    const int N = w->max_obj, T = N + 2, D = N + 2, Dp = pad4(T);
     const PackedLayout P(N, w->num_feats, w->feat_dim);
-    if (ws_bytes < aff_workspace_bytes(B, N)) {
+    const AffWs L(B, N);
+    if (ws_bytes < L.total) {
         set_error_msg("aff_softmax: workspace too small");
         return SHASTA_E_WORKSPACE;
     }
     if (B == 0) return SHASTA_OK;
     char* base = static_cast<char*>(ws);
-    float* matched = reinterpret_cast<float*>(base);
+    float* matched = reinterpret_cast<float*>(base + L.matched);
     const int M = B * T;
     int rc;
     // 32 rows per workgroup (RG = 2) halve the L2 -> register weight traffic per row, the limiter of this kernel (29 % matrix-
@@ -334,9 +318,9 @@ int aff_softmax(const shasta_weights* w, const float* packed, int B, const float
     if (pieces && !(w->options & SHASTA_OPT_TWO_PASS_AFF)) {
         // SHASTA_OPT_F16X2_AFF: the layers on fp16 pieces (aff_f16.hip: three products per fp32 product instead of six)
         if (w->options & SHASTA_OPT_F16X2_AFF)
-            rc = launch_aff_frame16(w, packed + P.aff16, residual, ld, matched_out ? matched : nullptr, Dp, m1, m2, B, base + aff_matched_bytes(B, N), st);
+            rc = launch_aff_frame16(w, packed + P.aff16, residual, ld, matched_out ? matched : nullptr, Dp, m1, m2, B, ws, st);
         else
-            rc = launch_aff_frame(w, packed + P.affp, residual, ld, matched_out ? matched : nullptr, Dp, m1, m2, B, base + aff_matched_bytes(B, N), st);
+            rc = launch_aff_frame(w, packed + P.affp, residual, ld, matched_out ? matched : nullptr, Dp, m1, m2, B, ws, st);
         if (rc) return rc;
     } else {
     if (pieces) {

@@ -466,21 +466,11 @@ __global__ __launch_bounds__(64 * WAVES) void aff_frame16_kernel(AffFrameArgs fa
     ap_frame_tail<ROWS, WAVES, true>(fa, smem, acc, b, q, nrows, g0, tid, lane, wid, reinterpret_cast<const float*>(a.wp) + ap16_scale_offset(5, a.D), rs);
 }
 
-size_t aff_frame_workspace_bytes(int B, int N);
-
 template <int ROWS, int WAVES>
 static int launch_aff_frame16_shape(AffFrameArgs& fa, int B, void* ws, hipStream_t st) {
     using S = AqShape<ROWS, WAVES>;
-    fa.G = cdiv(fa.p.T, ROWS);
-    unsigned* ctrl = static_cast<unsigned*>(ws);  // [status, ticket, arrive[B]]
-    fa.status = ctrl;
-    fa.ticket = ctrl + 1;
-    fa.arrive = ctrl + 2;
-    fa.part = reinterpret_cast<float*>(static_cast<char*>(ws) + aff_frame_ctrl_bytes(B));
-    if (hipMemsetAsync(ctrl, 0, (size_t)(B + 2) * sizeof(unsigned), st) != hipSuccess) {
-        set_error_msg("aff_frame16: memset of the control words failed");
-        return SHASTA_E_LAUNCH;
-    }
+    int rc = aff_frame_bind(fa, ROWS, B, ws, st, "aff_frame16");
+    if (rc) return rc;
     if (hipFuncSetAttribute((const void*)aff_frame16_kernel<ROWS, WAVES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S::LDS) != hipSuccess) {
         (void)hipGetLastError();
         set_error_msg("aff_frame16: the device refuses 160 KB of LDS per workgroup");
@@ -490,24 +480,11 @@ static int launch_aff_frame16_shape(AffFrameArgs& fa, int B, void* ws, hipStream
     return check_launch("aff_frame16");
 }
 
-// the six layers (fp16 pieces) and both softmaxes in one launch; packed16 = the aff16 section of the packed buffer
 int launch_aff_frame16(const shasta_weights* w, const float* packed16, const float* residual, int ld, float* matched, int ldm, float* m1,
                        float* m2, int B, void* ws, hipStream_t st) {
-    const int N = w->max_obj, T = N + 2, D = N + 2;
+    const int T = w->max_obj + 2;
     AffFrameArgs fa;
-    AffPiecesArgs& a = fa.p;
-    a.wp = reinterpret_cast<const uint32_t*>(packed16);
-    for (int i = 0; i < 6; ++i) a.bias[i] = w->aff[i].bias;
-    a.residual = residual;
-    a.matched = matched;
-    a.m1 = m1;
-    a.M = B * T;
-    a.T = T;
-    a.N = N;
-    a.D = D;
-    a.Dp = (T + 3) / 4 * 4;
-    a.ld = ld;
-    a.ldm = ldm;
+    aff_pieces_args(fa.p, w, packed16, residual, ld, matched, ldm, m1, B * T);
     fa.m2 = m2;
     return B * cdiv(T, 128) >= 256 ? launch_aff_frame16_shape<128, 8>(fa, B, ws, st) : launch_aff_frame16_shape<64, 4>(fa, B, ws, st);
 }

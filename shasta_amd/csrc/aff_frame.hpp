@@ -3,7 +3,7 @@
 // shasta.py:323-325) - the row softmax inside the workgroup, the column softmax through per-column partials exchanged between the
 // workgroups of a frame.
 #pragma once
-#include "common.hpp"
+#include "stages.hpp"
 #include "pair_layout.hpp"
 
 namespace shasta {
@@ -70,8 +70,40 @@ struct AffFrameArgs {
     int G;
 };
 
-// control words of a one-pass launch at the head of its workspace: [status, ticket, arrive[B]] (one memset per launch)
-__host__ __device__ inline size_t aff_frame_ctrl_bytes(int B) { return ((size_t)(B + 2) * sizeof(unsigned) + 255) / 256 * 256; }
+// host: the arguments every launcher of the piece kernels fills the same way; wp = the layers' section of the packed buffer, M rows
+inline void aff_pieces_args(AffPiecesArgs& a, const shasta_weights* w, const float* wp, const float* residual, int ld, float* matched, int ldm,
+                            float* m1, int M) {
+    a.wp = reinterpret_cast<const uint32_t*>(wp);
+    for (int i = 0; i < 6; ++i) a.bias[i] = w->aff[i].bias;
+    a.residual = residual;
+    a.matched = matched;
+    a.m1 = m1;
+    a.M = M;
+    a.T = a.D = w->max_obj + 2;
+    a.N = w->max_obj;
+    a.Dp = pad4(a.T);
+    a.ld = ld;
+    a.ldm = ldm;
+}
+
+// host: a one-pass launch with `rows` residual rows per workgroup on the aff workspace `ws` (AffWs) - row groups per frame, the control
+// words [status, ticket, arrive[B]] cleared by one memset on `st`, the column partials.  `who` prefixes the error message.
+inline int aff_frame_bind(AffFrameArgs& fa, int rows, int B, void* ws, hipStream_t st, const char* who) {
+    const AffWs L(B, fa.p.N);
+    fa.G = cdiv(fa.p.T, rows);
+    unsigned* ctrl = reinterpret_cast<unsigned*>(static_cast<char*>(ws) + L.ctrl);
+    fa.status = ctrl;
+    fa.ticket = ctrl + 1;
+    fa.arrive = ctrl + 2;
+    fa.part = reinterpret_cast<float*>(static_cast<char*>(ws) + L.part);
+    if (hipMemsetAsync(ctrl, 0, (size_t)(B + 2) * sizeof(unsigned), st) != hipSuccess) {
+        char msg[96];
+        snprintf(msg, sizeof(msg), "%s: memset of the control words failed", who);
+        set_error_msg(msg);
+        return SHASTA_E_LAUNCH;
+    }
+    return SHASTA_OK;
+}
 
 // the logical tile of this workgroup: tickets in start order when row groups wait for each other (G > 1), else the block id.
 // `slot`: four bytes of LDS nobody else touches until the second barrier.

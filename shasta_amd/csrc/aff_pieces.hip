@@ -460,25 +460,12 @@ static int launch_aff_pieces_shape(const AffPiecesArgs& a, hipStream_t st) {
     return check_launch("aff_pieces");
 }
 
-size_t aff_frame_workspace_bytes(int B, int N) {
-    const int T = N + 2, G = cdiv(T, 64);  // the 64-row shape needs the most partials
-    return aff_frame_ctrl_bytes(B) + align_up((size_t)B * G * 1024 * sizeof(float), 256);
-}
-
 template <int ROWS, int WAVES>
 static int launch_aff_frame_shape(AffFrameArgs& fa, int B, void* ws, hipStream_t st) {
     using S = ApShape<ROWS, WAVES>;
     const size_t lds = (size_t)S::ABYTES + S::BBYTES;
-    fa.G = cdiv(fa.p.T, ROWS);
-    unsigned* ctrl = static_cast<unsigned*>(ws);  // [status, ticket, arrive[B]]
-    fa.status = ctrl;
-    fa.ticket = ctrl + 1;
-    fa.arrive = ctrl + 2;
-    fa.part = reinterpret_cast<float*>(static_cast<char*>(ws) + aff_frame_ctrl_bytes(B));
-    if (hipMemsetAsync(ctrl, 0, (size_t)(B + 2) * sizeof(unsigned), st) != hipSuccess) {
-        set_error_msg("aff_frame: memset of the control words failed");
-        return SHASTA_E_LAUNCH;
-    }
+    int rc = aff_frame_bind(fa, ROWS, B, ws, st, "aff_frame");
+    if (rc) return rc;
     if (hipFuncSetAttribute((const void*)aff_frame_kernel<ROWS, WAVES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
         (void)hipGetLastError();
         set_error_msg("aff_frame: the device refuses 160 KB of LDS per workgroup");
@@ -488,44 +475,19 @@ static int launch_aff_frame_shape(AffFrameArgs& fa, int B, void* ws, hipStream_t
     return check_launch("aff_frame");
 }
 
-// the six layers and both softmaxes in one launch.  `matched` (B T x ldm, optional) receives the logits; ws: aff_frame_workspace_bytes
 int launch_aff_frame(const shasta_weights* w, const float* packed_pieces, const float* residual, int ld, float* matched, int ldm, float* m1,
                      float* m2, int B, void* ws, hipStream_t st) {
-    const int N = w->max_obj, T = N + 2, D = N + 2;
+    const int T = w->max_obj + 2;
     AffFrameArgs fa;
-    AffPiecesArgs& a = fa.p;
-    a.wp = reinterpret_cast<const uint32_t*>(packed_pieces);
-    for (int i = 0; i < 6; ++i) a.bias[i] = w->aff[i].bias;
-    a.residual = residual;
-    a.matched = matched;
-    a.m1 = m1;
-    a.M = B * T;
-    a.T = T;
-    a.N = N;
-    a.D = D;
-    a.Dp = (T + 3) / 4 * 4;
-    a.ld = ld;
-    a.ldm = ldm;
+    aff_pieces_args(fa.p, w, packed_pieces, residual, ld, matched, ldm, m1, B * T);
     fa.m2 = m2;
     return B * cdiv(T, 128) >= 256 ? launch_aff_frame_shape<128, 8>(fa, B, ws, st) : launch_aff_frame_shape<64, 4>(fa, B, ws, st);
 }
 
 int launch_aff_pieces(const shasta_weights* w, const float* packed_pieces, const float* residual, int ld, float* matched, int ldm,
                       float* m1, int M, hipStream_t st) {
-    const int N = w->max_obj, T = N + 2, D = N + 2, Dp = (T + 3) / 4 * 4;
     AffPiecesArgs a;
-    a.wp = reinterpret_cast<const uint32_t*>(packed_pieces);
-    for (int i = 0; i < 6; ++i) a.bias[i] = w->aff[i].bias;
-    a.residual = residual;
-    a.matched = matched;
-    a.m1 = m1;
-    a.M = M;
-    a.T = T;
-    a.N = N;
-    a.D = D;
-    a.Dp = Dp;
-    a.ld = ld;
-    a.ldm = ldm;
+    aff_pieces_args(a, w, packed_pieces, residual, ld, matched, ldm, m1, M);
     // 128-row workgroups once they fill the 256 CUs (0.825 ms against 0.837 ms for 257 k rows); below that the 64-row shape puts
     // twice as many workgroups on the chip
     return cdiv(M, 128) >= 256 ? launch_aff_pieces_shape<128, 8>(a, st) : launch_aff_pieces_shape<64, 4>(a, st);

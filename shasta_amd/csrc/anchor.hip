@@ -13,7 +13,7 @@
 // 16-byte loads (1 KiB per wave-instruction, fully coalesced), K is split across waves so that >= 4k waves stream
 // concurrently, and the split-K partials are summed in a fixed order afterwards (no float atomics -> bitwise
 // reproducible).
-#include "common.hpp"
+#include "stages.hpp"
 
 namespace shasta {
 
@@ -353,32 +353,6 @@ __global__ __launch_bounds__(256) void anchor_tail_small_kernel(AnchorTailArgs a
     }
 }
 constexpr int ANCHOR_TAIL_FUSED_MAX_B = 8;
-
-size_t anchor_split_workspace_bytes(int B, int K);
-bool anchor_split_serves(int B, int K, int x_batch_stride);
-void launch_split_x(const float* feat, const float* prev_feat, void* xs, int K, int B, int x_batch_stride, int np, const unsigned* xmax, bool precut,
-                    hipStream_t st);
-void launch_anchor_l1_split(const float* const W[4], const void* xs, float* part, int H, int K, int B, int* ks_out, int np,
-                            const unsigned* wmax, const void* wimg, hipStream_t st);
-int launch_x_maxima(const float* feat, const float* prev_feat, int K, int B, int x_batch_stride, unsigned* xmax, hipStream_t st);
-int launch_w_maxima(const float* const W[4], int H, int K, unsigned* wmax, float* sumabs, hipStream_t st);
-
-
-// [split-K partials, worst-case KS = 64][hidden (B, 4H)][bf16 activation image of anchor_split.hip, batches > 32 only]
-size_t bev_absmax_slot_bytes(int items);
-
-size_t anchor_shape_workspace_bytes(int B, int N, int F) {
-    const int H = N * F / 64;
-    return align_up((size_t)64 * B * 4 * H * sizeof(float), 256) + align_up((size_t)B * 4 * H * sizeof(float), 256) +
-           anchor_split_workspace_bytes(B, N * F) + align_up((size_t)2 * B * sizeof(int), 256) + align_up((size_t)4 * H * sizeof(int), 256) +
-           bev_absmax_slot_bytes(2 * B);
-}
-
-int launch_anchor_l1_mfma(const float* const W[4], const float* feat, const float* prev_feat, float* part, int H, int K,
-                          int B, int x_batch_stride, int* ks_out, hipStream_t st);
-int launch_gemm_nt_quad(const float* const A[4], const float* const W[4], const float* const bias[4], float* const C[4], int lda,
-                        int ldw, int ldc, int M, int N, int K, int act, hipStream_t st);
-bool gemm_nt_quad_direct_ok(const float* const A[4], const float* const W[4], int lda, int ldw, int K);
 constexpr int GEMM_DIRECT_MIN_B = 256;  // below, the VALU kernels of the small batches are as fast as the direct skinny GEMM (gemm_f32.hip)
 
 template <int BT, int R>
@@ -386,12 +360,6 @@ static void launch_l1(const AnchorL1Args& a, hipStream_t st) {
     const int G = 4 * a.groups_per_mlp;
     dim3 grid(cdiv(G * a.KS, 4), cdiv(a.B, BT));
     hipLaunchKernelGGL((anchor_l1_kernel<BT, R>), grid, dim3(256), 0, st, a);
-}
-
-// where anchor_shape leaves relu(W1 x + b1): (B, 4H), MLP-major inside a row; valid until the workspace is re-used
-const float* anchor_shape_hidden(const void* ws, int B, int N, int F) {
-    const size_t H = (size_t)N * F / 64;
-    return reinterpret_cast<const float*>(static_cast<const char*>(ws) + align_up((size_t)64 * B * 4 * H * sizeof(float), 256));
 }
 
 // the pre-cut piece image of the first-layer weights (SHASTA_OPT_PRECUT_WEIGHT_STREAM + a companion buffer built with it), or null
@@ -413,27 +381,14 @@ bool anchor_shape_uses_xmax(const shasta_weights* w, int B) {
     if (precut_image(w) && B >= PRECUT_MIN_BATCH) return true;
     return anchor_split_serves(B, N * F, (N + 2) * F) && B > 64;
 }
-// where anchor_shape keeps those maxima ([2 frames: feat, prev_feat][B] float bit patterns): a producer of the tables that already
-// knows them (the gather of shasta_affinity_from_bev_f32) writes them here and passes xmax_ready
-unsigned* anchor_shape_xmax(void* ws, int B, int N, int F) {
-    const size_t H = (size_t)N * F / 64;
-    char* hidden = static_cast<char*>(ws) + align_up((size_t)64 * B * 4 * H * sizeof(float), 256);
-    char* xs = hidden + align_up((size_t)B * 4 * H * sizeof(float), 256);
-    return reinterpret_cast<unsigned*>(xs + anchor_split_workspace_bytes(B, N * F));
-}
-// ... and the scratch lines the gather posts into before they are reduced to those maxima (bev_gather.hip): [2 B][slots][128 B]
-unsigned* anchor_shape_xmax_slots(void* ws, int B, int N, int F) {
-    const size_t H = (size_t)N * F / 64;
-    return reinterpret_cast<unsigned*>(reinterpret_cast<char*>(anchor_shape_xmax(ws, B, N, F)) + align_up((size_t)2 * B * sizeof(int), 256) +
-                                       align_up((size_t)4 * H * sizeof(int), 256));
-}
 
 // tail: the deferred box roles of anchor_boxes_impl; when given (small batches) everything behind the first layer goes into ONE launch
 static int anchor_shape_impl(const shasta_weights* w, int B, float* feat, float* prev_feat, void* ws, size_t ws_bytes, hipStream_t st,
                              hipEvent_t ev0, hipEvent_t ev1, const unsigned* wmax, bool xmax_ready, const BoxL2Args* tail) {
     const int N = w->max_obj, F = w->feat_dim;
     const int K = N * F, H = K / 64;
-    if (ws_bytes < anchor_shape_workspace_bytes(B, N, F)) {
+    const AnchorShapeWs L(B, N, F);
+    if (ws_bytes < L.total) {
         set_error_msg("anchor_shape: workspace too small");
         return SHASTA_E_WORKSPACE;
     }
@@ -453,15 +408,16 @@ static int anchor_shape_impl(const shasta_weights* w, int B, float* feat, float*
     int ks = max(1, min(min(64, cdiv(4096, G)), cdiv(K, 1024)));
     a.Kc = cdiv(cdiv(K, ks), 256) * 256;
     a.KS = cdiv(K, a.Kc);
-    float* part = static_cast<float*>(ws);
-    float* hidden = reinterpret_cast<float*>(static_cast<char*>(ws) + align_up((size_t)64 * B * 4 * H * sizeof(float), 256));
+    char* base = static_cast<char*>(ws);
+    float* part = reinterpret_cast<float*>(base + L.part);
+    float* hidden = reinterpret_cast<float*>(base + L.hidden);
     a.part = part;
     // B == 1: VALU weight-streaming GEMV (nothing to amortise; measured 6.8 TB/s).  2 <= B <= 32: the f32 matrix-core kernel
     // streams every weight once per 16 / 32 batch items at HBM speed (anchor_mfma.hip).  B > 32: the same fp32 arithmetic as
     // exact bf16 piece products, 64 / 128 items per weight pass (anchor_split.hip); with SHASTA_OPT_F32_WEIGHT_STREAM in
     // w->options the f32 MFMA kernel serves every B >= 2 (64 items per pass, matrix-pipe bound).  K = N*F is a multiple of 64.
     const bool force_f32 = (w->options & SHASTA_OPT_F32_WEIGHT_STREAM) != 0;
-    void* xs = reinterpret_cast<char*>(hidden) + align_up((size_t)B * 4 * H * sizeof(float), 256);
+    void* xs = base + L.xs;
     // the two-piece fp16 form when asked for: above 64 frame-pairs (up to 64 the three-piece bf16 kernel's 64-row pass is the faster one
     // while the weights are cut inside the kernel), and from PRECUT_MIN_BATCH frame-pairs when the pre-cut image is there: with nothing
     // but DMA, LDS reads and 6 / 12 MFMAs per 4 KB weight tile the small batches run at the speed of the stream as well
@@ -469,11 +425,13 @@ static int anchor_shape_impl(const shasta_weights* w, int B, float* feat, float*
     const bool f16x2 = anchor_shape_uses_xmax(w, B);
     const bool split = !force_f32 && (anchor_split_serves(B, K, a.x_batch_stride) || f16x2);
     const int np = f16x2 ? 2 : 3;
-    unsigned* xmax = reinterpret_cast<unsigned*>(static_cast<char*>(xs) + anchor_split_workspace_bytes(B, K));
+    // a producer of the tables that already knows the activation row maxima (the gather of shasta_affinity_from_bev_f32) has written
+    // them here and passes xmax_ready
+    unsigned* xmax = reinterpret_cast<unsigned*>(base + L.xmax);
     if (f16x2) {
         int rc0;
         if (!wmax) {  // stage entry point without a packed buffer: one extra pass over the weights into the workspace
-            unsigned* wm = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(xmax) + align_up((size_t)2 * B * sizeof(int), 256));
+            unsigned* wm = reinterpret_cast<unsigned*>(base + L.wmax);
             if ((rc0 = launch_w_maxima(a.W, H, K, wm, nullptr, st))) return rc0;
             wmax = wm;
         }
@@ -561,11 +519,6 @@ int anchor_shape(const shasta_weights* w, int B, float* feat, float* prev_feat, 
     return anchor_shape_impl(w, B, feat, prev_feat, ws, ws_bytes, st, ev0, ev1, wmax, xmax_ready, nullptr);
 }
 
-// [hidden (B, 4, HD)][packed box rows (2, B, ceil4(7N)) for the GEMM form]
-size_t anchor_boxes_workspace_bytes(int B, int N) {
-    return align_up((size_t)B * 4 * max(1, 7 * N / 32) * sizeof(float), 256) + align_up((size_t)2 * B * ((7 * N + 3) / 4 * 4) * sizeof(float), 256);
-}
-
 // defer: when given, the second layers / back-projection / tables are not launched but described there (anchor_shape_impl's tail)
 static int anchor_boxes_impl(const shasta_weights* w, int B, float* det_boxes, const float* prev_det_boxes, int box_stride,
                              float* det_tab, float* prev_tab, float* hid_ws, hipStream_t st, float* anchors_out, BoxL2Args* defer) {
@@ -584,12 +537,12 @@ static int anchor_boxes_impl(const shasta_weights* w, int B, float* det_boxes, c
         a.N = N;
         a.B = B;
         a.box_stride = box_stride;
-        const int ldx = (7 * N + 3) / 4 * 4;
+        const int ldx = pad4(7 * N);
         const float* W1d[4] = {a.W[0], a.W[1], a.W[2], a.W[3]};
         // (the packed box rows x7 are 16-byte aligned rows of ldx floats; the weights' rows are when 7 N % 4 == 0)
         const bool direct = B >= GEMM_DIRECT_MIN_B && gemm_nt_quad_direct_ok(W1d, W1d, ldx, 7 * N, 7 * N);
         if (B >= 256 || direct) {
-            float* x7 = reinterpret_cast<float*>(reinterpret_cast<char*>(hid_ws) + align_up((size_t)B * 4 * HD * sizeof(float), 256));
+            float* x7 = reinterpret_cast<float*>(reinterpret_cast<char*>(hid_ws) + AnchorBoxesWs(B, N).x7);
             hipLaunchKernelGGL(box_pack7_kernel, dim3(cdiv(ldx, 256), B, 2), dim3(256), 0, st, det_boxes, prev_det_boxes, x7, B, N, box_stride, ldx);
             int rc = check_launch("box_pack7");
             if (rc) return rc;
@@ -643,8 +596,8 @@ bool anchor_stage_fused_serves(const shasta_weights* w, int B) {
 int anchor_stage_fused(const shasta_weights* w, int B, float* feat, float* prev_feat, float* det_boxes, const float* prev_det_boxes,
                        int box_stride, float* det_tab, float* prev_tab, void* ws, size_t ws_bytes, hipStream_t st, hipEvent_t ev0,
                        hipEvent_t ev1, const unsigned* wmax, bool xmax_ready, float* anchors_out) {
-    const size_t shape_bytes = anchor_shape_workspace_bytes(B, w->max_obj, w->feat_dim);
-    if (ws_bytes < shape_bytes + anchor_boxes_workspace_bytes(B, w->max_obj)) {
+    const size_t shape_bytes = AnchorShapeWs(B, w->max_obj, w->feat_dim).total;
+    if (ws_bytes < shape_bytes + AnchorBoxesWs(B, w->max_obj).total) {
         set_error_msg("anchor stages: workspace too small");
         return SHASTA_E_WORKSPACE;
     }

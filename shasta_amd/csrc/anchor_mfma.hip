@@ -19,7 +19,7 @@
 // cycles.  The loop below is VALU-free (scalar base + 32-bit lane offset addressing); in-kernel stamps
 // (a clock-stamp build, removed after commit 96899a8) read 2200 cycles per tile at 64 rows = 93 % of the matrix pipe, at an in-kernel clock
 // of 1.98 GHz (32 rows: 1140 of 1024 cycles at 1.72 GHz - the chip lowers its clock under the combined HBM + MFMA load).  Split-K partials are reduced afterwards in a fixed order.
-#include "common.hpp"
+#include "stages.hpp"
 #include "lds_dma.hpp"
 
 #include <type_traits>

@@ -17,7 +17,7 @@
 // Sync: one s_barrier per tile.  Wave w waits (counted vmcnt) for its own share of tile t+1, then the barrier certifies
 // (a) every share of x tile t+1 has landed and (b) every wave has finished reading tile t out of its slot, which is then
 // refilled with tile t+NS.  Workgroups that share an x stream (same K chunk, same frame) sit on one XCD (blockIdx.x % 8).
-#include "common.hpp"
+#include "stages.hpp"
 #include "lds_dma.hpp"
 #include "pieces.hpp"
 

@@ -9,7 +9,7 @@
 // output row [pt0 C | pt1 C | ...] is written directly in the packed (N, num_point*C) order the
 // reference builds with a cat of sections (bird_eye_view.py:35-37).
 // HBM-bound: 4*C*4 B read + C*4 B written per point.
-#include "common.hpp"
+#include "stages.hpp"
 
 namespace shasta {
 
@@ -174,8 +174,8 @@ int launch_absmax_finalize(const unsigned* slots, unsigned* out, int items, hipS
 // bev2 / boxes2 / out2 / absmax2: null, or the pair's other frame (same shapes and strides), gathered by the same launch
 int launch_bev_gather(const float* bev, int B, int H, int W, int C, const float* boxes, int N, int box_stride, int box_batch_stride,
                       int num_point, float pc_x0, float pc_y0, float vs_x, float vs_y, float out_stride, float* out, int out_row_stride,
-                      int out_batch_stride, unsigned* absmax, hipStream_t st, const float* bev2 = nullptr, const float* boxes2 = nullptr,
-                      float* out2 = nullptr, unsigned* absmax2 = nullptr) {
+                      int out_batch_stride, unsigned* absmax, hipStream_t st, const float* bev2, const float* boxes2, float* out2,
+                      unsigned* absmax2) {
     const long total = (long)B * N * num_point;
     if (total == 0) return SHASTA_OK;
     SHASTA_REQUIRE(total < (1L << 30), "bev_gather: too many points");

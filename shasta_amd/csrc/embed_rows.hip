@@ -15,7 +15,7 @@
 // fp32 staging [256][ET + 8] (row values + the row's box) over the ring -> 32 threads per row add bias and box part, take the row maximum and store the row.
 #include <algorithm>
 
-#include "common.hpp"
+#include "stages.hpp"
 #include "lds_dma.hpp"
 #include "pair_layout.hpp"
 #include "pieces.hpp"
@@ -28,12 +28,7 @@ namespace shasta {
 // (tools/gpu_kernel_ab.sh; <64, 2>: 0.77, <128, 4, three slots> = one workgroup per CU again: 0.67).  Results are the same bits - a
 // wavefront's arithmetic does not depend on the shape.
 
-// fragments per side: [feature block NFB][k step F/16][piece 3][64 lanes] x 16 B
-size_t embed_packed_floats(int F) {
-    const PairDims d(F);
-    const int nfb = (d.H1 + d.R1 + 31) / 32;
-    return (size_t)2 * nfb * (F / 16) * 3 * 256;
-}
+// fragments per side: [feature block NFB][k step F/16][piece 3][64 lanes] x 16 B (the embp section of PackedLayout)
 
 struct EmbedPackArgs {
     const float* w[2];  // [E12][F] row-major: prev / cur feature columns of fuse_shape.0 | res_coeff.0 (PackedLayout wemb_*)

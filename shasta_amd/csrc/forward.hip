@@ -1,41 +1,7 @@
 // C-ABI entry points of the affinity forward: argument checks, workspace carving, stage sequencing.
-#include "common.hpp"
-#include "pair_layout.hpp"
+#include "stages.hpp"
 
 namespace shasta {
-size_t anchor_shape_workspace_bytes(int B, int N, int F);
-size_t anchor_boxes_workspace_bytes(int B, int N);
-size_t pair_workspace_bytes(int B, int N, int F);
-size_t aff_workspace_bytes(int B, int N);
-const float* anchor_shape_hidden(const void* ws, int B, int N, int F);
-int anchor_shape(const shasta_weights* w, int B, float* feat, float* prev_feat, void* ws, size_t ws_bytes, hipStream_t st,
-                 hipEvent_t ev0, hipEvent_t ev1, const unsigned* wmax, bool xmax_ready);
-bool anchor_shape_uses_xmax(const shasta_weights* w, int B);
-unsigned* anchor_shape_xmax(void* ws, int B, int N, int F);
-unsigned* anchor_shape_xmax_slots(void* ws, int B, int N, int F);
-size_t bev_absmax_slot_bytes(int items);
-int launch_absmax_finalize(const unsigned* slots, unsigned* out, int items, hipStream_t st);
-int launch_bev_gather(const float* bev, int B, int H, int W, int C, const float* boxes, int N, int box_stride, int box_batch_stride,
-                      int num_point, float pc_x0, float pc_y0, float vs_x, float vs_y, float out_stride, float* out, int out_row_stride,
-                      int out_batch_stride, unsigned* absmax, hipStream_t st, const float* bev2, const float* boxes2, float* out2,
-                      unsigned* absmax2);
-int anchor_boxes(const shasta_weights* w, int B, float* det_boxes, const float* prev_det_boxes, int box_stride,
-                 float* det_tab, float* prev_tab, float* hid_ws, hipStream_t st, float* anchors_out);
-bool anchor_stage_fused_serves(const shasta_weights* w, int B);
-int anchor_stage_fused(const shasta_weights* w, int B, float* feat, float* prev_feat, float* det_boxes, const float* prev_det_boxes,
-                       int box_stride, float* det_tab, float* prev_tab, void* ws, size_t ws_bytes, hipStream_t st, hipEvent_t ev0,
-                       hipEvent_t ev1, const unsigned* wmax, bool xmax_ready, float* anchors_out);
-int pair_residual(const shasta_weights* w, const float* packed, int B, const float* feat, const float* prev_feat,
-                  const float* det_tab, const float* prev_tab, float* residual, int ld, void* ws, size_t ws_bytes,
-                  hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
-int aff_status(const shasta_weights* w, int B, int ld, const void* ws, int* status, hipStream_t st);
-int aff_softmax(const shasta_weights* w, const float* packed, int B, const float* residual, int ld, float* m1,
-                float* m2, float* matched_out, void* ws, size_t ws_bytes, hipStream_t st);
-int pack_weights(const shasta_weights* w, float* packed, hipStream_t st);
-int launch_w_maxima(const float* const W[4], int H, int K, unsigned* wmax, float* sumabs, hipStream_t st);
-size_t precut_image_bytes(int H, int K);
-int launch_precut_weights(const float* const W[4], const unsigned* wmax, void* img, int H, int K, hipStream_t st);
-
 static int check_weights(const shasta_weights* w) {
     SHASTA_REQUIRE(w, "null weights");
     SHASTA_REQUIRE(w->max_obj >= 1 && w->max_obj <= 2046, "max_obj out of range (1..2046)");
@@ -68,17 +34,16 @@ static int check_weights(const shasta_weights* w) {
 struct FwdWs {
     size_t anchor, boxes, pair, aff, residual, total;
     FwdWs(int B, int N, int F) {
-        const int T = N + 2, Dp = (T + 3) / 4 * 4;
-        anchor = anchor_shape_workspace_bytes(B, N, F);
-        boxes = anchor_boxes_workspace_bytes(B, N);
-        pair = pair_workspace_bytes(B, N, F);
-        aff = aff_workspace_bytes(B, N);
-        residual = align_up((size_t)B * T * Dp * sizeof(float), 256);
+        const int T = N + 2;
+        anchor = AnchorShapeWs(B, N, F).total;
+        boxes = AnchorBoxesWs(B, N).total;
+        pair = PairWs(B, N, F).total;
+        aff = AffWs(B, N).total;
+        residual = align_up((size_t)B * T * pad4(T) * sizeof(float), 256);
         // anchor / pair / aff scratch is live one stage at a time -> shared region (the two anchor stages side by side: small batches run
         // them interleaved, anchor_stage_fused)
         size_t stage = anchor + boxes > pair ? anchor + boxes : pair;
         stage = stage > aff ? stage : aff;
-        stage = stage > boxes ? stage : boxes;
         total = stage + residual;
     }
 };
@@ -169,7 +134,7 @@ extern "C" int shasta_anchor_boxes_f32(const shasta_weights* w, int B, float* de
     if (rc) return rc;
     SHASTA_REQUIRE(B >= 0 && det_boxes && prev_det_boxes && det_tab && prev_tab && workspace, "anchor_boxes: bad argument");
     SHASTA_REQUIRE(box_stride >= 10, "anchor_boxes: box rows need [x,y,z,w,l,h,yaw,vx,vy,dt]");
-    if (workspace_bytes < anchor_boxes_workspace_bytes(B, w->max_obj)) {
+    if (workspace_bytes < AnchorBoxesWs(B, w->max_obj).total) {
         set_error_msg("anchor_boxes: workspace too small");
         return SHASTA_E_WORKSPACE;
     }
@@ -207,7 +172,7 @@ extern "C" int shasta_aff_status(const shasta_weights* w, int B, int ld_residual
     int rc = check_weights(w);
     if (rc) return rc;
     SHASTA_REQUIRE(B >= 0 && workspace && status, "aff_status: bad argument");
-    if (workspace_bytes < aff_workspace_bytes(B, w->max_obj)) {
+    if (workspace_bytes < AffWs(B, w->max_obj).total) {
         set_error_msg("aff_status: workspace too small");
         return SHASTA_E_WORKSPACE;
     }
@@ -219,7 +184,7 @@ extern "C" int shasta_forward_status(const shasta_weights* w, int B, const void*
     int rc = check_weights(w);
     if (rc) return rc;
     SHASTA_REQUIRE(B >= 0 && workspace && status, "forward_status: bad argument");
-    const int N = w->max_obj, T = N + 2, Dp = (T + 3) / 4 * 4;
+    const int N = w->max_obj, Dp = pad4(N + 2);
     const FwdWs L(B, N, w->feat_dim);
     if (workspace_bytes < L.total) {
         set_error_msg("forward_status: workspace too small");
@@ -249,7 +214,7 @@ static int forward_impl(const shasta_weights* w, const void* packed, int B, floa
     SHASTA_REQUIRE(box_stride >= 10, "forward: box rows need [x,y,z,w,l,h,yaw,vx,vy,dt]");
     SHASTA_REQUIRE(((uintptr_t)feat | (uintptr_t)prev_feat | (uintptr_t)packed | (uintptr_t)workspace) % 16 == 0,
                    "forward: feat/prev_feat/packed/workspace must be 16-byte aligned");
-    const int N = w->max_obj, F = w->feat_dim, T = N + 2, Dp = (T + 3) / 4 * 4;
+    const int N = w->max_obj, F = w->feat_dim, T = N + 2, Dp = pad4(T);
     const FwdWs L(B, N, F);
     if (workspace_bytes < L.total) {
         set_error_msg("forward: workspace too small");
@@ -258,7 +223,8 @@ static int forward_impl(const shasta_weights* w, const void* packed, int B, floa
     if (B == 0) return SHASTA_OK;
     hipStream_t st = as_stream(stream);
     float* residual = static_cast<float*>(workspace);
-    void* stage = static_cast<char*>(workspace) + L.residual;
+    char* stage = static_cast<char*>(workspace) + L.residual;
+    const AnchorShapeWs A(B, N, F);
     const size_t stage_bytes = L.total - L.residual;
     const float* pk = static_cast<const float*>(packed);
     bool xmax_ready = false;
@@ -267,7 +233,7 @@ static int forward_impl(const shasta_weights* w, const void* packed, int B, floa
         // largest magnitude of every batch item where anchor_shape looks for it (no separate pass over the tables)
         unsigned* slots = nullptr;
         if (anchor_shape_uses_xmax(w, B)) {
-            slots = anchor_shape_xmax_slots(stage, B, N, F);
+            slots = reinterpret_cast<unsigned*>(stage + A.slots);
             if (hipMemsetAsync(slots, 0, bev_absmax_slot_bytes(2 * B), st) != hipSuccess) return SHASTA_E_LAUNCH;
             xmax_ready = true;
         }
@@ -277,7 +243,7 @@ static int forward_impl(const shasta_weights* w, const void* packed, int B, floa
                                     src->vs_x, src->vs_y, src->out_stride, feat, F, T * F, slots, st, src->prev_bev, prev_det_boxes, prev_feat,
                                     slots ? slots + bev_absmax_slot_bytes(B) / sizeof(unsigned) : nullptr)))
             return rc;
-        if (slots && (rc = launch_absmax_finalize(slots, anchor_shape_xmax(stage, B, N, F), 2 * B, st))) return rc;
+        if (slots && (rc = launch_absmax_finalize(slots, reinterpret_cast<unsigned*>(stage + A.xmax), 2 * B, st))) return rc;
     }
     if (!shape_hidden_out && anchor_stage_fused_serves(w, B) && !anchor_shape_uses_xmax(w, B)) {
         // one or a few frame-pairs: three launches less (the training path wants the hidden activations materialised: the long form)
@@ -290,14 +256,14 @@ static int forward_impl(const shasta_weights* w, const void* packed, int B, floa
             return rc;
         if (shape_hidden_out) {  // training: the backward re-uses the hidden activations instead of re-streaming the weights
             const size_t H = (size_t)N * F / 64;
-            hipError_t e = hipMemcpyAsync(shape_hidden_out, anchor_shape_hidden(stage, B, N, F), (size_t)B * 4 * H * sizeof(float),
+            hipError_t e = hipMemcpyAsync(shape_hidden_out, stage + A.hidden, (size_t)B * 4 * H * sizeof(float),
                                           hipMemcpyDeviceToDevice, st);
             if (e != hipSuccess) {
                 set_error("forward: copy anchor hidden", e);
                 return SHASTA_E_LAUNCH;
             }
         }
-        if ((rc = anchor_boxes(w, B, det_boxes, prev_det_boxes, box_stride, det_tab, prev_tab, static_cast<float*>(stage), st,
+        if ((rc = anchor_boxes(w, B, det_boxes, prev_det_boxes, box_stride, det_tab, prev_tab, reinterpret_cast<float*>(stage), st,
                                src ? src->anchor_boxes_out : nullptr)))
             return rc;
     }

@@ -8,7 +8,7 @@
 // (16 VGPRs); K is walked in 32-wide slices staged through LDS (row stride 33 floats: the one-float-per-lane
 // fragment reads A[i=l&31][k=l>>5] then hit 32 distinct banks), next slice prefetched into registers while
 // the current one is multiplied.
-#include "common.hpp"
+#include "stages.hpp"
 
 namespace shasta {
 
@@ -162,8 +162,8 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_small_dual_kernel(GemmNtDual 
     }
 }
 
-int launch_gemm_nt(const float* A, int lda, const float* W, int ldw, const float* bias, float* C, int ldc, int M,
-                   int N, int K, int act, hipStream_t st) {
+static int launch_gemm_nt(const float* A, int lda, const float* W, int ldw, const float* bias, float* C, int ldc, int M,
+                          int N, int K, int act, hipStream_t st) {
     if (M == 0 || N == 0) return SHASTA_OK;
     dim3 grid(cdiv(N, BN), cdiv(M, BM));
     const bool vec = (lda % 4 == 0) && (ldw % 4 == 0) && (((uintptr_t)A | (uintptr_t)W) % 16 == 0);
@@ -579,9 +579,9 @@ __global__ __launch_bounds__(256) void gemm_reduce_group_kernel(const float* __r
     gemm_reduce_body(part + (size_t)blockIdx.y * nz * stride, stride, nz, gg.C[blockIdx.y], n, N, ldc, gg.bias[blockIdx.y], act);
 }
 
-int launch_gemm_strided(const float* A, long sa_m, long sa_k, const float* W, long sw_n, long sw_k, const float* bias,
-                        const float* mask, int ldmask, float* C, int ldc, int M, int N, int K, int act, float* splitk_ws,
-                        size_t splitk_ws_bytes, hipStream_t st) {
+static int launch_gemm_strided(const float* A, long sa_m, long sa_k, const float* W, long sw_n, long sw_k, const float* bias,
+                               const float* mask, int ldmask, float* C, int ldc, int M, int N, int K, int act, float* splitk_ws,
+                               size_t splitk_ws_bytes, hipStream_t st) {
     if (M == 0 || N == 0) return SHASTA_OK;
     GemmS g;
     g.A = A; g.W = W; g.bias = bias; g.mask = mask; g.C = C;
@@ -624,9 +624,9 @@ int launch_gemm_strided(const float* A, long sa_m, long sa_k, const float* W, lo
 
 // `count` products of one shape in one launch (two with a split reduction); every member as launch_gemm_strided would compute it alone
 // when given count-th of the scratch
-int launch_gemm_strided_group(int count, const float* const* A, const float* const* W, const float* const* bias, const float* const* mask,
-                              float* const* C, long sa_m, long sa_k, long sw_n, long sw_k, int ldmask, int ldc, int M, int N, int K, int act,
-                              float* splitk_ws, size_t splitk_ws_bytes, hipStream_t st) {
+static int launch_gemm_strided_group(int count, const float* const* A, const float* const* W, const float* const* bias, const float* const* mask,
+                                     float* const* C, long sa_m, long sa_k, long sw_n, long sw_k, int ldmask, int ldc, int M, int N, int K, int act,
+                                     float* splitk_ws, size_t splitk_ws_bytes, hipStream_t st) {
     if (M == 0 || N == 0 || count == 0) return SHASTA_OK;
     GemmS g;
     GemmGroup gg;

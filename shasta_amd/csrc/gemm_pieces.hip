@@ -131,8 +131,8 @@ __global__ __launch_bounds__(256) void gemm_nt_pieces_kernel(GemmPieces g) {
 }
 
 // One problem (A1 == nullptr) or two independent problems of the same shape in one launch.
-int launch_gemm_nt_pieces(const float* A0, const float* W0, const float* bias0, float* C0, const float* A1, const float* W1,
-                          const float* bias1, float* C1, int lda, int ldw, int ldc, int M, int N, int K, int act, hipStream_t st) {
+static int launch_gemm_nt_pieces(const float* A0, const float* W0, const float* bias0, float* C0, const float* A1, const float* W1,
+                                 const float* bias1, float* C1, int lda, int ldw, int ldc, int M, int N, int K, int act, hipStream_t st) {
     if (M == 0 || N == 0) return SHASTA_OK;
     GemmPieces g{{A0, A1}, {W0, W1}, {bias0, bias1}, {C0, C1}, lda, ldw, ldc, M, N, K, act};
     uintptr_t al = (uintptr_t)A0 | (uintptr_t)W0;

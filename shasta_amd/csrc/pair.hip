@@ -12,7 +12,7 @@
 //   pair_mfma4<F, WPB>  lane = pair: h1 = relu(UP[t]+UC[d]), layers 2-4 on v_mfma_f32_4x4x1_16B_f32 -> residual
 // (Two other formulations - a 16x16x4 accumulator-chained MFMA kernel and a packed-VALU kernel with SGPR weights - measured
 // within 4 % of this one and were removed from the product library after round 1; they are in the history of this file.)
-#include "common.hpp"
+#include "stages.hpp"
 #include "pair_layout.hpp"
 
 namespace shasta {
@@ -501,58 +501,24 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(4))) v
     }
 }
 
-size_t pair_workspace_bytes(int B, int N, int F) {
-    const PairDims d(F);
-    const int T = N + 2, Dp = (T + 3) / 4 * 4;
-    size_t s = 0;
-    s += 2 * align_up((size_t)B * T * d.ET * sizeof(float), 256);  // UP, UC
-    s += 2 * align_up((size_t)B * T * 16 * sizeof(float), 256);    // hand tables
-    s += align_up((size_t)B * T * sizeof(float), 256);             // column norms
-    (void)Dp;
-    return s;
-}
-
-int pair_f16_pack(const shasta_weights* w, float* out, hipStream_t st);
-int launch_pair_f16(const float* packed, const float* p16, const float* UP, const float* UC, const float* hand_prev,
-                    const float* hand_det, const float* denom, float* residual, int B, int T, int D, int ld, int nf, bool grid,
-                    hipStream_t st);
-bool pair_f16w_serves(int F);
-int pair_f16w_pack(const shasta_weights* w, float* out, hipStream_t st);
-int launch_pair_f16w(const float* packed, const float* p16, const float* UP, const float* UC, const float* hand_prev,
-                     const float* hand_det, const float* denom, float* residual, int B, int T, int D, int ld, int F, hipStream_t st);
-int launch_gemm_nt(const float* A, int lda, const float* W, int ldw, const float* bias, float* C, int ldc, int M,
-                   int N, int K, int act, hipStream_t st);
-int launch_gemm_nt_dual(const float* A0, const float* W0, const float* bias0, float* C0, const float* A1, const float* W1,
-                        const float* bias1, float* C1, int lda, int ldw, int ldc, int M, int N, int K, int act, hipStream_t st);
-int launch_gemm_nt_pieces(const float* A0, const float* W0, const float* bias0, float* C0, const float* A1, const float* W1,
-                          const float* bias1, float* C1, int lda, int ldw, int ldc, int M, int N, int K, int act, hipStream_t st);
-
-int embed_pack(const shasta_weights* w, float* packed, hipStream_t st);
-bool embed_rows_serves(int F);
-int launch_embed_rows(const shasta_weights* w, const float* packed, const float* prev_feat, const float* feat, const float* prev_tab,
-                      const float* det_tab, float* UP, float* UC, float* hand_prev, float* hand_det, int M, hipStream_t st);
-
 int pair_residual(const shasta_weights* w, const float* packed, int B, const float* feat, const float* prev_feat,
                   const float* det_tab, const float* prev_tab, float* residual, int ld, void* ws, size_t ws_bytes,
                   hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
     const int N = w->max_obj, F = w->feat_dim, nf = w->num_feats, T = N + 2, D = N + 2;
     const PairDims d(F);
     const PackedLayout P(N, nf, F);
-    if (ws_bytes < pair_workspace_bytes(B, N, F)) {
+    const PairWs L(B, N, F);
+    if (ws_bytes < L.total) {
         set_error_msg("pair_residual: workspace too small");
         return SHASTA_E_WORKSPACE;
     }
     if (B == 0) return SHASTA_OK;
     char* base = static_cast<char*>(ws);
-    float* UP = reinterpret_cast<float*>(base);
-    base += align_up((size_t)B * T * d.ET * sizeof(float), 256);
-    float* UC = reinterpret_cast<float*>(base);
-    base += align_up((size_t)B * T * d.ET * sizeof(float), 256);
-    float* hand_prev = reinterpret_cast<float*>(base);
-    base += align_up((size_t)B * T * 16 * sizeof(float), 256);
-    float* hand_det = reinterpret_cast<float*>(base);
-    base += align_up((size_t)B * T * 16 * sizeof(float), 256);
-    float* denom = reinterpret_cast<float*>(base);
+    float* UP = reinterpret_cast<float*>(base + L.up);
+    float* UC = reinterpret_cast<float*>(base + L.uc);
+    float* hand_prev = reinterpret_cast<float*>(base + L.hand_prev);
+    float* hand_det = reinterpret_cast<float*>(base + L.hand_det);
+    float* denom = reinterpret_cast<float*>(base + L.denom);
 
     // row embeddings UP / UC: from 8192 table rows one fused kernel per launch forms the feature part on the bf16-piece matrix path,
     // adds the box columns and takes the row maxima (embed_rows.hip); below that the 64-row f32 GEMM tiles fill the chip better and
@@ -652,8 +618,6 @@ int pair_residual(const shasta_weights* w, const float* packed, int B, const flo
     return check_launch("pair_mfma4");
 }
 
-int aff_pieces_pack(const shasta_weights* w, float* out, hipStream_t st);
-int aff_f16_pack(const shasta_weights* w, float* out, hipStream_t st);
 int pack_weights(const shasta_weights* w, float* packed, hipStream_t st) {
     PackArgs a;
     for (int i = 0; i < 4; ++i) a.fs[i] = w->fuse_shape[i];

@@ -19,7 +19,7 @@
 // Range: the scale 2^e of a track is the one that puts (max |UP[t]| + max over the tile's detections of max |UC[d]|) - an upper
 // bound of every h1 of the sub-steps - into (2^13, 2^14]; the row maxima come from embed_rows / row_prep (slot 13 of the hand rows).  The
 // second-layer weights are cut once at pack time with one exponent per MLP (pair_f16_pack_kernel).
-#include "common.hpp"
+#include "stages.hpp"
 #include "pair_layout.hpp"
 #include "pieces.hpp"
 
@@ -43,8 +43,6 @@ struct A4h {
 // (8 x 32, rows 8..15 zero); lane (i = lane & 15, kb = lane >> 4) holds W[i][32 ks + 8 kb + j] * 2^e_mlp; high pieces then low pieces.
 // layout (dwords): [piece 2][fragment 4][lane 64][4], then 3 int exponents (fs, rc, fd), padded to 4.
 constexpr int P16_FRAG_DW = 2 * 4 * 64 * 4;
-constexpr int P16_DW = P16_FRAG_DW + 4;
-size_t pair_f16_packed_floats() { return P16_DW; }
 
 struct PairF16PackArgs {
     const float* w_fs2;  // fuse_shape.2.weight (16, 32)
@@ -544,7 +542,7 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
     }
 }
 
-size_t pair_f16_lds_bytes(int wpb, bool grid) {
+static size_t pair_f16_lds_bytes(int wpb, bool grid) {
     constexpr PairDims dm(256);
     const size_t base = ((size_t)64 * (dm.ET + 4) + ((a4_total(256) + 3) & ~3) + (size_t)wpb * 3 * 256 + (size_t)wpb * 64 * PF_TS) * sizeof(float);
     // GRID: the fp16 piece tile is 1 KB larger than the fp32 tile, + 512 bytes of UP pieces per wave

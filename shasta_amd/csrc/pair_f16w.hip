@@ -29,7 +29,7 @@
 // v_cvt_pk_f16_f32 at 5.3 / 5.3 / 8.1 / 7 / 7 / 8.1 cycles per two values) = ~4200: with two waves per SIMD the matrix pipe is busy
 // ~85 % of the time at the ~1.7 GHz the power cap leaves under this load - removing vector work (the in-place UP scaling below:
 // -68 instructions) moved the time by 1.6 %.
-#include "common.hpp"
+#include "stages.hpp"
 #include "pair_layout.hpp"
 #include "pieces.hpp"
 
@@ -428,7 +428,7 @@ __global__ __launch_bounds__(64 * PWK_WPB) __attribute__((amdgpu_waves_per_eu(2,
     }
 }
 
-size_t pair_f16w_lds_bytes(int F) {
+static size_t pair_f16w_lds_bytes(int F) {
     return ((size_t)((a4_total(F) + 3) & ~3) + (size_t)PWK_WPB * 6 * PWK_SLOT) * sizeof(float) + (size_t)PW<320>::FRAG_DW * 4;
 }
 

@@ -92,6 +92,9 @@ SH_HD constexpr size_t ap16_scale_offset(int layer, int D) {
 }
 SH_HD constexpr size_t ap16_total(int D) { return ap16_scale_offset(6, D); }
 
+// n rounded up to a multiple of 4: the padded width Dp of a table of T = N + 2 columns (16-byte aligned rows)
+SH_HD constexpr int pad4(int n) { return (n + 3) / 4 * 4; }
+
 // Packed buffer sections (float offsets).  Dp = padded aff width (multiple of 4).
 struct PackedLayout {
     int F, nf, N, D, Dp, E12, ET;
@@ -102,7 +105,7 @@ struct PackedLayout {
         nf = num_feats;
         N = max_obj;
         D = max_obj + 2;
-        Dp = (D + 3) / 4 * 4;
+        Dp = pad4(D);
         E12 = d.H1 + d.R1;
         ET = d.ET;
         size_t o = 0;

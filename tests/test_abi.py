@@ -55,6 +55,15 @@ def test_size_queries_do_not_need_a_gpu():
     assert lib.shasta_voxelize_workspace_bytes(300000, 160000, 10) > 160000 * 10 * 4
     # ... + the cell -> first point hash table: 2^20 (key, index) pairs for 3e5 points - not the reference's 332 MB dense map
     assert lib.shasta_voxelize_workspace_bytes(300000, 160000, 10) < 160000 * 10 * 4 + 3 * 300000 * 4 + (1 << 20) * 8 + (1 << 16)
+    # exact values: the stage workspaces are carved from one layout struct each (csrc/stages.hpp); a section that moves or grows
+    # shows here before any kernel runs (batches on both sides of the 8 / 17 / 32 / 64 frame-pair switches of the anchor stage)
+    for B, want in ((1, 3156480), (17, 151441664), (65, 399689728), (1024, 4771699968)):
+        assert lib.shasta_forward_workspace_bytes(B, 500, 7, 256) == want
+    assert lib.shasta_forward_workspace_bytes(9, 90, 7, 320) == 26710016
+    assert lib.shasta_forward_workspace_bytes(33, 90, 7, 320) == 38932736
+    assert lib.shasta_packed_bytes(500, 7, 256) == 2326928 and lib.shasta_packed_bytes(90, 7, 320) == 1340096
+    assert [lib.shasta_aug_shape_aux_bytes(500, 256, o) for o in (0, 8, 40)] == [64256, 64256, 4128832256]
+    assert lib.shasta_voxelize_workspace_bytes(300000, 160000, 10) == 18393856
 
 
 def test_missing_library_fails_loudly(monkeypatch):

@@ -52,7 +52,7 @@ int main(int argc, char** argv) {
     }
     float *packed, *packed16, *res[2], *matched, *m1, *m2, *m1o;
     void* ws;
-    const size_t wsb = shasta::aff_frame_workspace_bytes(B, N);
+    const size_t wsb = shasta::AffWs(B, N).total;  // the one-pass launchers take the whole aff workspace
     hipMalloc(&packed, shasta::ap_layer_offset(6, D) * 256 * 4);
     hipMalloc(&packed16, shasta::ap16_total(D) * 4);
     hipMalloc(&res[0], (size_t)M * Dp * 4 + 4096);
