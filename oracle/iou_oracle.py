@@ -7,16 +7,19 @@ PARITY UNPINNED against the reference: the reference computes the polygon inters
 not installed here and not vendored; the rotated-IoU C++/CUDA code under det3d/ops/iou3d_nms needs CUDA headers and is
 unbuildable in this image.  The intersection of two convex quadrilaterals is restated with Sutherland-Hodgman clipping
 (any exact algorithm yields the same area up to rounding); the convex hull uses scipy.spatial.ConvexHull exactly like the
-reference.  The oracle is pinned by closed-form known answers instead (tests/test_iou.py).
+reference.  The oracle is pinned by closed-form known answers instead (tests/test_iou.py) and, since the clip and the kernel's
+restate one another, against exact geometry: tests/test_geometry_exact.py holds its clip and hull areas to a quarter of the
+float64 bar of a 60-digit evaluation (tests/exact_geometry.py) at degenerate poses and world offsets up to 1e5 m.
 Only tests/ may import this module.
 """
 import numpy as np
 from scipy.spatial import ConvexHull
 
 
-def corners2d(b):
-    """b = [x, y, z, o, l, w, h] -> (4, 2) corners pc0..pc3 (bbox.py:70-84)."""
+def corners2d(b, origin=(0.0, 0.0)):
+    """b = [x, y, z, o, l, w, h] -> (4, 2) corners pc0..pc3 (bbox.py:70-84), in the frame whose origin is `origin`."""
     x, y, _, o, l, w, _ = (float(v) for v in b[:7])
+    x, y = x - float(origin[0]), y - float(origin[1])
     c, s = np.cos(o), np.sin(o)
     p0 = np.array([x + c * l / 2 + s * w / 2, y + s * l / 2 - c * w / 2])
     p1 = np.array([x + c * l / 2 - s * w / 2, y + s * l / 2 + c * w / 2])
@@ -62,8 +65,14 @@ def clip_convex(subject, clip):
     return np.array(out) if out else np.zeros((0, 2))
 
 
+def pair_corners(a, b):
+    """Corners of both boxes in the frame of a's centre, like the kernel: areas are translation invariant, and there their rounding
+    is that of the boxes' size instead of that of their world coordinates (tests/test_geometry_exact.py holds it to the exact area)."""
+    return corners2d(a, a[:2]), corners2d(b, a[:2])
+
+
 def intersection_area(a, b):
-    return poly_area(clip_convex(corners2d(a), corners2d(b)))
+    return poly_area(clip_convex(*pair_corners(a, b)))
 
 
 def _heights(a, b):
@@ -82,14 +91,17 @@ def iou3d(a, b):
     return vol / (union + 1e-5)
 
 
+def hull_area(a, b):
+    pts = np.vstack(pair_corners(a, b))
+    return poly_area(pts[ConvexHull(pts).vertices])
+
+
 def giou3d(a, b):
     """geometry.py:208-231."""
     oh, uh = _heights(a, b)
     I = intersection_area(a, b) * oh
     U = float(a[5]) * float(a[4]) * float(a[6]) + float(b[5]) * float(b[4]) * float(b[6]) - I
-    pts = np.vstack([corners2d(a), corners2d(b)])
-    hull = ConvexHull(pts)
-    C = poly_area(pts[hull.vertices]) * uh
+    C = hull_area(a, b) * uh
     return I / U - (C - U) / C
 
 

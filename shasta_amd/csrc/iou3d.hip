@@ -9,8 +9,9 @@
 
 namespace shasta {
 
-__device__ __forceinline__ void corners2d(const double* b, P2* c) {
-    const double x = b[0], y = b[1], o = b[3], l = b[4], w = b[5];
+// corners of box b in the frame whose origin is (ox, oy)
+__device__ __forceinline__ void corners2d(const double* b, double ox, double oy, P2* c) {
+    const double x = b[0] - ox, y = b[1] - oy, o = b[3], l = b[4], w = b[5];
     const double cs = cos(o), sn = sin(o);
     c[0] = {x + cs * l / 2 + sn * w / 2, y + sn * l / 2 - cs * w / 2};
     c[1] = {x + cs * l / 2 - sn * w / 2, y + sn * l / 2 + cs * w / 2};
@@ -56,9 +57,12 @@ __global__ void iou3d_matrix_kernel(const double* __restrict__ dets, const doubl
     const double* a = dets + (size_t)d * stride;
     const double* b = trks + (size_t)t * stride;
     P2 ca[4], cb[4];
-    corners2d(a, ca);
-    corners2d(b, cb);
-    const double inter = clip_area(ca, cb);
+    // Both boxes in the frame of A's centre: the difference of two nearby centres is (nearly) exact, so the areas carry the
+    // rounding of the boxes' size, eps * L^2, not that of their world coordinates, eps * C^2 (C up to thousands of metres).
+    corners2d(a, a[0], a[1], ca);
+    corners2d(b, a[0], a[1], cb);
+    // the overlap cannot exceed either footprint: a box of zero length or width overlaps nothing, exactly
+    const double inter = fmin(clip_area(ca, cb), fmin(a[4] * a[5], b[4] * b[5]));
     const double za = a[2], zb = b[2], ha = a[6], hb = b[6];
     const double d1 = (za + ha / 2) - (zb - hb / 2), d2 = (zb + hb / 2) - (za - ha / 2);
     const double oh = fmax(0.0, fmin(d1, d2));

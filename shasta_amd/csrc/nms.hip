@@ -19,8 +19,10 @@
 
 namespace shasta {
 
-__device__ __forceinline__ void bev_corners(const float* b, P2* c) {
-    const double cx = b[0], cy = b[1], hx = 0.5 * (double)b[3], hy = 0.5 * (double)b[4];
+// corners of box b in the frame whose origin is (ox, oy): callers pass the centre of the pair's first box, so that the clip works
+// on coordinates of the boxes' size whatever their world position (the difference of the float32 centres of two boxes that can touch is exact in float64)
+__device__ __forceinline__ void bev_corners(const float* b, double ox, double oy, P2* c) {
+    const double cx = (double)b[0] - ox, cy = (double)b[1] - oy, hx = 0.5 * (double)b[3], hy = 0.5 * (double)b[4];
     const double cs = cos((double)b[6]), sn = sin((double)b[6]);
     const double ux[4] = {-hx, hx, hx, -hx}, uy[4] = {-hy, -hy, hy, hy};
 #pragma unroll
@@ -33,8 +35,8 @@ __device__ __forceinline__ double iou_bev(const float* a, const float* b) {
     const double ra = 0.5 * sqrt((double)a[3] * a[3] + (double)a[4] * a[4]), rb = 0.5 * sqrt((double)b[3] * b[3] + (double)b[4] * b[4]);
     if (dx * dx + dy * dy > (ra + rb) * (ra + rb)) return 0.0;
     P2 ca[4], cb[4];
-    bev_corners(a, ca);
-    bev_corners(b, cb);
+    bev_corners(a, (double)a[0], (double)a[1], ca);
+    bev_corners(b, (double)a[0], (double)a[1], cb);
     const double ov = clip_area(ca, cb);
     const double sa = (double)a[3] * a[4], sb = (double)b[3] * b[4];
     return ov / fmax(sa + sb - ov, 1e-8);
@@ -146,8 +148,8 @@ __global__ __launch_bounds__(256) void boxes_bev_kernel(const float* __restrict_
         const double dx = (double)a[0] - b[0], dy = (double)a[1] - b[1];
         const double ra = 0.5 * sqrt((double)a[3] * a[3] + (double)a[4] * a[4]), rb = 0.5 * sqrt((double)b[3] * b[3] + (double)b[4] * b[4]);
         if (dx * dx + dy * dy <= (ra + rb) * (ra + rb)) {
-            bev_corners(a, ca);
-            bev_corners(b, cb);
+            bev_corners(a, (double)a[0], (double)a[1], ca);
+            bev_corners(b, (double)a[0], (double)a[1], cb);
             ovd = clip_area(ca, cb);
         }
     }

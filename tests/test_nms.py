@@ -71,18 +71,21 @@ def test_device_nms_edges_and_pcdet_wrapper():
 
 
 @pytest.mark.gpu
-def test_device_nms_many_boxes_analytic_chain():
-    """6000 unit squares on a line, 0.6 apart: only neighbours overlap (IoU = 0.4 / 1.6 = 0.25), so the greedy result is
-    computable without an N x N matrix.  Exercises more than one 64-word slot per lane of the reduction kernel."""
+@pytest.mark.parametrize("n", [4096, 4097, 6000, 8192, 8193, 16384, 16385, 32768])
+@pytest.mark.parametrize("form", ["nms_gpu", "nms_normal_gpu"])
+def test_device_nms_many_boxes_analytic_chain(form, n):
+    """n unit squares on a line, 0.6 apart: only neighbours overlap (IoU = 0.4 / 1.6 = 0.25; float32 centres move it by 1e-3 at most),
+    so the greedy result is computable without an N x N matrix.  The sizes sit on both sides of every step of the reduction kernel's
+    mask words per lane: 1 (n <= 4096), 2 (<= 8192), 4 (<= 16384) and 8 (<= 32768, the documented limit: a 128 MiB mask)."""
     from shasta_amd import nms
-    n = 6000
+    fn = getattr(nms, form)
     rng = np.random.default_rng(0)
     boxes = np.zeros((n, 7), np.float32)
     boxes[:, 0] = 0.6 * np.arange(n)
     boxes[:, 3:6] = 1.0
     scores = rng.permutation(n).astype(np.float32)
     dev = torch.device("cuda:0")
-    sel, _ = nms.nms_gpu(torch.from_numpy(boxes).to(dev), torch.from_numpy(scores).to(dev), 0.2)
+    sel, _ = fn(torch.from_numpy(boxes).to(dev), torch.from_numpy(scores).to(dev), 0.2)
     removed = np.zeros(n, bool)
     want = []
     for k in np.argsort(-scores, kind="stable"):
@@ -93,8 +96,29 @@ def test_device_nms_many_boxes_analytic_chain():
             if 0 <= j < n:
                 removed[j] = True
     assert sel.cpu().numpy().tolist() == want
-    sel2, _ = nms.nms_gpu(torch.from_numpy(boxes).to(dev), torch.from_numpy(scores).to(dev), 0.3)  # above every IoU
+    sel2, _ = fn(torch.from_numpy(boxes).to(dev), torch.from_numpy(scores).to(dev), 0.3)  # above every IoU
     assert sel2.numel() == n
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("entry", ["shasta_nms_rotated_f32", "shasta_nms_normal_f32"])
+def test_device_nms_refuses_more_than_32768_boxes(entry):
+    """One box over the limit, every buffer large enough for it: an error code, the message names the limit, num_keep is not written."""
+    from shasta_amd import hip
+    lib = hip.load()
+    n = 32769
+    dev = torch.device("cuda:0")
+    boxes = torch.zeros(n, 7, device=dev)
+    boxes[:, 0] = 2.0 * torch.arange(n, device=dev)
+    boxes[:, 3:6] = 1.0
+    keep = torch.full((n,), -7, dtype=torch.int32, device=dev)
+    num = torch.full((1,), -7, dtype=torch.int32, device=dev)
+    ws_bytes = lib.shasta_nms_workspace_bytes(n)
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=dev)
+    rc = getattr(lib, entry)(hip.ptr(boxes), n, 0.5, hip.ptr(ws), ws_bytes, hip.ptr(keep), hip.ptr(num), hip.stream_ptr())
+    torch.cuda.synchronize()
+    assert rc != 0 and "32768" in lib.shasta_last_error().decode()
+    assert int(num.item()) == -7 and bool((keep == -7).all())
 
 
 # ---- the rest of the reference module's surface: boxes_iou_bev / boxes_iou3d_gpu / nms_normal_gpu (parity unpinned: see oracle header) ----
