@@ -1,7 +1,7 @@
 // K4/K5: pair residual.  Restates det3d/models/tracker/shasta.py:277-319:
 //   hand-designed residuals (:277-283), fuse_shape (:286-290), fuse_det (:293-307), res_coeff (:310-316) and the
 //   weighted sum residual = alpha*fused + beta*dist + omega*shape (:319), for all T x D (track, detection) pairs.
-// See pair_layout.hpp for the factorisation and the MFMA operand chaining.
+// See pair_layout.hpp for the factorisation and the MFMA operand chaining, pair_lane.hpp for what the three pair kernels share.
 //
 // Kernels (per forward):
 //   pack_pair_weights   once per weight load: fragments + factorised first-layer matrices
@@ -13,7 +13,7 @@
 // (Two other formulations - a 16x16x4 accumulator-chained MFMA kernel and a packed-VALU kernel with SGPR weights - measured
 // within 4 % of this one and were removed from the product library after round 1; they are in the history of this file.)
 #include "stages.hpp"
-#include "pair_layout.hpp"
+#include "pair_lane.hpp"
 
 namespace shasta {
 
@@ -285,7 +285,7 @@ __global__ __launch_bounds__(256) void row_prep_kernel(RowPrepArgs a) {
         const f32x4* bp = reinterpret_cast<const f32x4*>(a.tab[which] + (size_t)row * 8);
         const f32x4 b0 = bp[0], b1 = bp[1];
         f32x4* h = reinterpret_cast<f32x4*>(a.hand[which] + (size_t)row * 16);
-        // (box slots >= num_feats are zero in both tables' hand rows: pair_layout.hpp, hand_dist)
+        // (box slots >= num_feats are zero in both tables' hand rows: pair_lane.hpp, hand_dist)
         const int nf = a.nf;
         h[0] = f32x4{b0[0], nf > 1 ? b0[1] : 0.0f, nf > 2 ? b0[2] : 0.0f, nf > 3 ? b0[3] : 0.0f};
         h[1] = f32x4{nf > 4 ? b1[0] : 0.0f, nf > 5 ? b1[1] : 0.0f, nf > 6 ? b1[2] : 0.0f, 0.0f};
@@ -315,13 +315,19 @@ __global__ __launch_bounds__(256) void row_prep_kernel(RowPrepArgs a) {
 // Against the 16x16x4 chain: output widths only round up to 4 (not 16): 512 MFMAs x 8.4 = 4.3k cycles per 64 pairs
 // instead of 4 x 44 x 32 = 5.6k, and ~330 VALU instructions per 64 pairs instead of ~540.
 // ------------------------------------------------------------------------------------------------------------
-#define MFMA4(a, b, c) __builtin_amdgcn_mfma_f32_4x4x1f32((a), (b), (c), 0, 0, 0)
-
-template <int F, int L>
-struct A4 {
-    static constexpr LayerDesc D = layer_desc(F, L);
-    static constexpr int NOB = a4_nob(F, L), KG = a4_kg(F, L), OFF = a4_offset(F, L), KIN = D.kin, BIAS = NOB * KG * 16;
+// dynamic LDS of pair_mfma4_kernel (float offsets): the kernel carves it, the launcher sizes it
+template <int F, int WPB, int DT>
+struct PairMfma4Lds {
+    static constexpr int US = PairDims(F).ET + 4;      // floats per row of the detection tile
+    static constexpr int RING = 3 * (64 / DT);         // UP row slots per wave: the rows in use, and two iterations ahead
+    static constexpr int uc = 0;                       // [DT][US]
+    static constexpr int a4 = uc + DT * US;            // [a4_total(F)]
+    static constexpr int up = a4 + pad4(a4_total(F));  // [WPB][RING][UP_SLOT]
+    static constexpr size_t bytes = (size_t)(up + WPB * RING * UP_SLOT) * sizeof(float);
 };
+static_assert(PairMfma4Lds<64, 8, 64>::bytes == 49760 && PairMfma4Lds<64, 8, 32>::bytes == 63584 &&
+              PairMfma4Lds<256, 8, 64>::bytes == 66800 && PairMfma4Lds<256, 8, 32>::bytes == 74480 &&
+              PairMfma4Lds<320, 8, 64>::bytes == 74336 && PairMfma4Lds<320, 8, 32>::bytes == 79968, "the sizes the launcher spelt out before");
 
 // DT = detections per wave: 64 (one track per iteration), or 32 with TWO tracks per iteration (lanes 32..63 take track t + 1): the
 // same instruction stream covers 2 x 32 pairs, so a table of D = 92 rows (the shipped car configuration: max_obj 90) fills 3 x 32
@@ -339,19 +345,19 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(4))) v
                                                          float* __restrict__ residual, int T, int D, int ld, int nf,
                                                          int TW) {
     constexpr PairDims dm(F);
-    constexpr int H1 = dm.H1, R1 = dm.R1, ET = dm.ET, US = ET + 4;
-    constexpr int NA4 = a4_total(F);
+    constexpr int H1 = dm.H1, R1 = dm.R1, ET = dm.ET;
+    using Lds = PairMfma4Lds<F, WPB, DT>;
+    constexpr int US = Lds::US, RING = Lds::RING;
     static_assert(DT == 64 || DT == 32, "64 detections x 1 track or 32 detections x 2 tracks per wave");
     constexpr int TPI = 64 / DT;       // tracks per iteration
-    constexpr int RING = 3 * TPI;      // UP row slots per wave: the rows in use, and two iterations ahead
     extern __shared__ __attribute__((aligned(16))) float s_dyn4[];
-    float* s_uc = s_dyn4;              // [DT][US]
-    float* s_a4 = s_dyn4 + DT * US;    // [NA4]
-    // UP rows (the per-track half of the first layers) of the next two tracks, per wave: [WPB][3 slots][256 floats].  They
+    float* s_uc = s_dyn4 + Lds::uc;
+    float* s_a4 = s_dyn4 + Lds::a4;
+    // UP rows (the per-track half of the first layers) of the next two tracks, per wave.  They
     // were scalar loads before; SMEM and LDS share lgkmcnt, so every s_load had to be waited for with lgkmcnt(0) before the
     // next LDS result could be used - nine full scalar-memory latencies per track (measured: 25 % of the wave time parked).
     // An LDS-DMA (counted on vmcnt) fetches row t+2 while row t is in use; the values are then read back as LDS broadcasts.
-    float* s_up = s_dyn4 + DT * US + ((NA4 + 3) & ~3);
+    float* s_up = s_dyn4 + Lds::up;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int dlane = lane & (DT - 1), th = lane / DT;  // detection of the tile, track of the iteration
@@ -359,7 +365,6 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(4))) v
     xcd_logical_block(lbx, lby, b);  // the detection tiles of a frame on one XCD (common.hpp)
     const int d0 = lbx * DT;
     const int d = d0 + dlane, dcl = min(d, D - 1);
-    const PackedLayout P(0, 0, F);
     {
         const f32x4* src = reinterpret_cast<const f32x4*>(UC);
 #pragma unroll 4
@@ -367,39 +372,28 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(4))) v
             const int r = e / (ET / 4), c = e - r * (ET / 4);
             *reinterpret_cast<f32x4*>(&s_uc[r * US + 4 * c]) = src[((size_t)b * D + min(d0 + r, D - 1)) * (ET / 4) + c];
         }
-        const f32x4* asrc = reinterpret_cast<const f32x4*>(packed + P.a4);
-#pragma unroll 2
-        for (int e = tid; e < NA4 / 4; e += 64 * WPB) reinterpret_cast<f32x4*>(s_a4)[e] = asrc[e];
+        a4_stage<F, 64 * WPB>(packed, s_a4, tid);
     }
     float hd[12];
-    {
-        const f32x4* h = reinterpret_cast<const f32x4*>(hand_det + ((size_t)b * D + dcl) * 16);
-        const f32x4 a = h[0], c = h[1], e = h[2], g = h[3];
-        hd[0] = a[0]; hd[1] = a[1]; hd[2] = a[2]; hd[3] = a[3]; hd[4] = c[0]; hd[5] = c[1]; hd[6] = c[2];
-        hd[7] = e[0]; hd[8] = e[1]; hd[9] = e[2]; hd[10] = e[3]; hd[11] = g[0];
-    }
+    (void)load_hand_det(hand_det + ((size_t)b * D + dcl) * 16, hd);  // (the row's maximum is for the fp16 kernels)
     const float dnm = denom[(size_t)b * D + dcl], rdn = 1.0f / dnm;
     __syncthreads();
     const float* ucrow = s_uc + dlane * US;
-    typedef __attribute__((address_space(3))) float lfloat;
-    typedef __attribute__((address_space(3))) f32x4 lf32x4;
-    // LDS byte address of this lane's row i = lane & 3 inside every [i][kk] group of the A table
-    const unsigned arow_base = (unsigned)(unsigned long long)(s_a4 + (lane & 3) * 4);
-    const unsigned abias_base = (unsigned)(unsigned long long)(s_a4 + (lane & 3));
-    const f32x4 zero4 = {0, 0, 0, 0};
+    const A4Lane a4l(s_a4, lane);
 
     const int t_beg = (lby * WPB + wid) * TW;
     const int t_end = min(T, t_beg + TW);
-    float* my_up = s_up + wid * (RING * 256);
+    float* my_up = s_up + wid * (RING * UP_SLOT);
     // lanes [0, ET/4): the UP row; the next 4 lanes: the 16-float hand row of the same track (lands right behind it); the
     // remaining lanes repeat the last UP chunk (their LDS words are unused)
     const bool hp_lane = lane >= ET / 4 && lane < ET / 4 + 4;
     const int up_lane = 4 * min(lane, ET / 4 - 1), hp_off = 4 * (lane - ET / 4);
+    // (one copy per kernel: as a function in pair_lane.hpp it changed this kernel's schedule)
     auto dma_up = [&](int row, int slot) {
         const size_t r = (size_t)b * T + min(row, T - 1);
         const float* src = hp_lane ? hand_prev + r * 16 + hp_off : UP + r * ET + up_lane;
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                         (__attribute__((address_space(3))) void*)(my_up + slot * 256), 16, 0, 0);
+                                         (__attribute__((address_space(3))) void*)(my_up + slot * UP_SLOT), 16, 0, 0);
     };
     if (t_beg < t_end) {
 #pragma unroll
@@ -412,10 +406,10 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(4))) v
 #pragma unroll
         for (int i = 0; i < TPI; ++i) dma_up(t + 2 * TPI + i, (t - t_beg + 2 * TPI + i) % RING);
         const int tt = t + th;  // this lane's track
-        unsigned upo = (unsigned)(unsigned long long)(my_up + ((t - t_beg + th) % RING) * 256);
+        unsigned upo = (unsigned)(unsigned long long)(my_up + ((t - t_beg + th) % RING) * UP_SLOT);
         asm volatile("" : "+v"(upo));
         const lfloat* up = (const lfloat*)(unsigned long long)upo;
-        float hp[16];
+        float hp[16];  // (read back here: through a function of pair_lane.hpp the register allocation moved)
         {
             const f32x4 h0 = *reinterpret_cast<const lf32x4*>(up + ET), h1 = *reinterpret_cast<const lf32x4*>(up + ET + 4),
                         h2 = *reinterpret_cast<const lf32x4*>(up + ET + 8), h3 = *reinterpret_cast<const lf32x4*>(up + ET + 12);
@@ -427,25 +421,15 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(4))) v
                 hp[12 + k] = h3[k];
             }
         }
-        // the A table is loop invariant: an opaque copy of its address per track keeps the 128 ds_read_b128 inside the
-        // loop instead of 512 hoisted registers
-        unsigned ao = arow_base, bo = abias_base;
-        asm volatile("" : "+v"(ao), "+v"(bo));
-        const lfloat* arow = (const lfloat*)(unsigned long long)ao;
-        const lfloat* abias = (const lfloat*)(unsigned long long)bo;
+        const lfloat *arow, *abias;
+        a4l.per_track(arow, abias);
 
-        // bias: acc[ob] = bias[4*ob + i] * 1
-        auto init = [&](auto tag, f32x4* acc) {
-            using AL = decltype(tag);
-#pragma unroll
-            for (int ob = 0; ob < AL::NOB; ++ob) acc[ob] = MFMA4(abias[AL::OFF + AL::BIAS + ob * 4], 1.0f, zero4);
-        };
         // layer 1 (factorised) feeding layer 2.  (Forming UP[t] + UC[d] on the matrix pipe - one 4x4x1 MFMA with B = 1.0 and
         // C = the UC float4 per 4 features instead of 4 v_add - was measured in round 2: 7.15 - 7.27 ms against 6.31 - 6.51 ms
         // for this form on the same box, 512 frame-pairs per launch; the adds stay on the VALU.)
         auto layer12 = [&](auto tag, int seg, f32x4* acc) {
             using AL = decltype(tag);
-            init(tag, acc);
+            a4_init<AL>(abias, acc);
 #pragma unroll
             for (int kg = 0; kg < AL::KG; ++kg) {
                 const f32x4 u = *reinterpret_cast<const f32x4*>(ucrow + seg + 4 * kg);
@@ -463,40 +447,20 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(4))) v
                 }
             }
         };
-        // acc = bias + W . relu(in): the k-th input is register k & 3 of the previous layer's block k >> 2
-        auto layer = [&](auto tag, const f32x4* in, f32x4* acc) {
-            using AL = decltype(tag);
-            init(tag, acc);
-#pragma unroll
-            for (int kg = 0; kg < AL::KG; ++kg) {
-                f32x4 a4[AL::NOB];
-#pragma unroll
-                for (int ob = 0; ob < AL::NOB; ++ob) a4[ob] = *reinterpret_cast<const lf32x4*>(arow + AL::OFF + (ob * AL::KG + kg) * 16);
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                    if (4 * kg + kk < AL::KIN) {
-                        const float h = relu_nan(in[kg][kk]);
-#pragma unroll
-                        for (int ob = 0; ob < AL::NOB; ++ob) acc[ob] = MFMA4(a4[ob][kk], h, acc[ob]);
-                    }
-                }
-            }
-        };
         f32x4 a_rc2[A4<F, L_RC2>::NOB], a_rc3[A4<F, L_RC3>::NOB];
         f32x4 a_fs2[A4<F, L_FS2>::NOB], a_fs3[A4<F, L_FS3>::NOB], a_fs4[A4<F, L_FS4>::NOB];
         f32x4 a_fd2[A4<F, L_FD2>::NOB], a_fd3[A4<F, L_FD3>::NOB];
         layer12(A4<F, L_RC2>{}, H1, a_rc2);
         layer12(A4<F, L_FS2>{}, 0, a_fs2);
         layer12(A4<F, L_FD2>{}, H1 + R1, a_fd2);
-        layer(A4<F, L_RC3>{}, a_rc2, a_rc3);
-        layer(A4<F, L_FS3>{}, a_fs2, a_fs3);
-        layer(A4<F, L_FD3>{}, a_fd2, a_fd3);
-        layer(A4<F, L_FS4>{}, a_fs3, a_fs4);
+        a4_layer<A4<F, L_RC3>, A4_RELU_NAN>(arow, abias, a_rc2, a_rc3);
+        a4_layer<A4<F, L_FS3>, A4_RELU_NAN>(arow, abias, a_fs2, a_fs3);
+        a4_layer<A4<F, L_FD3>, A4_RELU_NAN>(arow, abias, a_fd2, a_fd3);
+        a4_layer<A4<F, L_FS4>, A4_RELU_NAN>(arow, abias, a_fs3, a_fs4);
 
         // ---- hand-designed residual (shasta.py:277-283) ----
         const float dist = hand_dist(hp, hd, dnm, rdn);
-        // ---- combine (shasta.py:316-319) ----
-        const float res = (a_rc3[0][0] * a_fd3[0][0] + a_rc3[0][1] * dist) + a_rc3[0][2] * a_fs4[0][0];
+        const float res = pair_combine(a_rc3[0], a_fd3[0][0], dist, a_fs4[0][0]);
         if (d < D && tt < t_end) residual[((size_t)b * T + tt) * ld + d] = res;
     }
 }
@@ -591,10 +555,10 @@ int pair_residual(const shasta_weights* w, const float* packed, int B, const flo
     // iteration per wave: the prologue is repeated, but 24 workgroups finish in a third of the time of 3 (31 -> ~10 us at D = 92)
     while ((long)B * cdiv(D, dt) * ny < 256 && cdiv(T, wpb * ny * 2) >= tpi) ny *= 2;
     const int tw = cdiv(cdiv(T, wpb * ny), tpi) * tpi;
-    const size_t lds = ((size_t)dt * (d.ET + 4) + ((a4_total(F) + 3) & ~3) + (size_t)wpb * 3 * tpi * 256) * sizeof(float);
     dim3 grid(cdiv(D, dt), cdiv(T, wpb * tw), B);
 #define SHASTA_LAUNCH_PAIR4_DT(FF, DD)                                                                                                    \
     do {                                                                                                                                  \
+        constexpr size_t lds = PairMfma4Lds<FF, wpb, DD>::bytes;                                                                          \
         if (lds > 64 * 1024)                                                                                                              \
             (void)hipFuncSetAttribute((const void*)pair_mfma4_kernel<FF, wpb, DD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         hipLaunchKernelGGL((pair_mfma4_kernel<FF, wpb, DD>), grid, dim3(64 * wpb), lds, st, packed, UP, UC, hand_prev, hand_det, denom,   \

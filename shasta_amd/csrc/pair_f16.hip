@@ -20,20 +20,10 @@
 // bound of every h1 of the sub-steps - into (2^13, 2^14]; the row maxima come from embed_rows / row_prep (slot 13 of the hand rows).  The
 // second-layer weights are cut once at pack time with one exponent per MLP (pair_f16_pack_kernel).
 #include "stages.hpp"
-#include "pair_layout.hpp"
+#include "pair_lane.hpp"
 #include "pieces.hpp"
 
-#include <type_traits>
-
 namespace shasta {
-
-#define MFMA4(a, b, c) __builtin_amdgcn_mfma_f32_4x4x1f32((a), (b), (c), 0, 0, 0)
-
-template <int F, int L>
-struct A4h {
-    static constexpr LayerDesc D = layer_desc(F, L);
-    static constexpr int NOB = a4_nob(F, L), KG = a4_kg(F, L), OFF = a4_offset(F, L), KIN = D.kin, BIAS = NOB * KG * 16;
-};
 
 // (fma2_relu01, f16_res_lo / _hi: every result passes through the packed multiply or v_cvt_pk_f16_f32 before it reaches an MFMA -
 // hazard rule of pieces.hpp)
@@ -43,13 +33,6 @@ struct A4h {
 // (8 x 32, rows 8..15 zero); lane (i = lane & 15, kb = lane >> 4) holds W[i][32 ks + 8 kb + j] * 2^e_mlp; high pieces then low pieces.
 // layout (dwords): [piece 2][fragment 4][lane 64][4], then 3 int exponents (fs, rc, fd), padded to 4.
 constexpr int P16_FRAG_DW = 2 * 4 * 64 * 4;
-
-struct PairF16PackArgs {
-    const float* w_fs2;  // fuse_shape.2.weight (16, 32)
-    const float* w_rc2;  // res_coeff.2.weight (16, 64)
-    const float* w_fd2;  // fuse_det.2.weight (8, 32)
-    uint32_t* out;
-};
 
 __global__ __launch_bounds__(256) void pair_f16_pack_kernel(PairF16PackArgs a) {
     __shared__ float red[3][4];
@@ -65,30 +48,34 @@ __global__ __launch_bounds__(256) void pair_f16_pack_kernel(PairF16PackArgs a) {
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = i < rows ? __builtin_ldexpf(W[mlp][i * kin + 32 * ks + 8 * kb + j], ex[mlp]) : 0.0f;
-    u32x4 hi, lo;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const _Float16 h0 = (_Float16)v[2 * j], h1 = (_Float16)v[2 * j + 1];
-        const f16x2 hh = {h0, h1};
-        hi[j] = __builtin_bit_cast(uint32_t, hh);
-        lo[j] = cvt_f16x2(v[2 * j] - (float)h0, v[2 * j + 1] - (float)h1);
-    }
-    reinterpret_cast<u32x4*>(a.out)[(0 * 4 + frag) * 64 + lane] = hi;
-    reinterpret_cast<u32x4*>(a.out)[(1 * 4 + frag) * 64 + lane] = lo;
+    store_weight_pieces(v, a.out, 4, frag, lane);
 }
 
 int pair_f16_pack(const shasta_weights* w, float* out, hipStream_t st) {
-    PairF16PackArgs a;
-    a.w_fs2 = w->fuse_shape[1].weight;
-    a.w_rc2 = w->res_coeff[1].weight;
-    a.w_fd2 = w->fuse_det[1].weight;
-    a.out = reinterpret_cast<uint32_t*>(out);
-    hipLaunchKernelGGL(pair_f16_pack_kernel, dim3(1), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(pair_f16_pack_kernel, dim3(1), dim3(256), 0, st, pair_f16_pack_args(w, out));
     return check_launch("pair_f16_pack");
 }
 
 // ---- the kernel (F = 256: H1 = 32, R1 = 64, fuse_det 32; H2 = 16, R2 = 16, 8) ---------------------------------------------
 constexpr int PF_TS = 44;  // floats per pair in the transposition tile: 40 + 4 pad (conflict-free b128 reads at stride 44)
+constexpr int GR_ROW = 136;  // GRID: fp16 per row of the detection tile: 128 + 8 pad (272 B)
+
+// dynamic LDS of pair_f16_kernel (float offsets): the kernel carves it, the launcher sizes it.  GRID: the detection tile holds fp16
+// pieces - [64][GR_ROW] high pieces, then the same of low pieces, 1 KB more than the fp32 tile - and every wave has a row of UP pieces
+// behind the transposition tiles
+template <int WPB, bool GRID>
+struct PairF16Lds {
+    static constexpr int US = PairDims(256).ET + 4;               // floats per row of the fp32 detection tile
+    static constexpr int uc = 0;                                  // [64][US], GRID: [2][64][GR_ROW / 2] words
+    static constexpr int ucl = uc + 64 * (GR_ROW / 2);            // GRID: the low pieces
+    // [a4_total(256)] 4x4x1 operand table (layers 3-4 and the layer-2 biases)
+    static constexpr int a4 = uc + (GRID ? 2 * 64 * (GR_ROW / 2) : 64 * US);
+    static constexpr int up = a4 + pad4(a4_total(256));           // [WPB][3 slots][UP_SLOT]
+    static constexpr int tr = up + WPB * 3 * UP_SLOT;             // [WPB][64 pairs][PF_TS]
+    static constexpr int upp = tr + WPB * 64 * PF_TS;             // GRID: [WPB][2][64] words
+    static constexpr size_t bytes = (size_t)(upp + (GRID ? WPB * 128 : 0)) * sizeof(float);
+};
+static_assert(PairF16Lds<8, false>::bytes == 156912 && PairF16Lds<8, true>::bytes == 162032, "the sizes the launcher spelt out before");
 
 // GRID (SHASTA_OPT_F16GRID_PAIR, opt-in): the pieces of h1 are not cut per pair.  UP[t] and UC[d] are cut ONCE per row into two
 // fp16 pieces on a common fixed grid per MLP - high piece an integer, low piece a multiple of 2^-11, after scaling the largest
@@ -109,27 +96,19 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
     // SIMD do not advance at the same rate)
     constexpr int F = 256;
     constexpr PairDims dm(F);
-    constexpr int ET = dm.ET, US = ET + 4;
+    constexpr int ET = dm.ET;
     static_assert(dm.H1 == 32 && dm.R1 == 64 && ET == 128 && dm.H2 == 16 && dm.R2 == 16, "pair_f16_kernel is laid out for F = 256");
-    constexpr int NA4 = a4_total(F);
+    using Lds = PairF16Lds<WPB, GRID>;
+    constexpr int US = Lds::US;
     extern __shared__ __attribute__((aligned(16))) float s_dynh[];
-    float* s_uc = s_dynh;                                  // [64][US]
-    float* s_a4 = s_dynh + 64 * US;                        // [NA4] 4x4x1 operand table (layers 3-4 and the layer-2 biases)
-    float* s_up = s_a4 + ((NA4 + 3) & ~3);                 // [WPB][3 slots][256 floats]
-    float* s_tr = s_up + WPB * 3 * 256;                    // [WPB][64 pairs][PF_TS]
-    // GRID: the tile holds fp16 pieces instead: [64][GR_ROW] high pieces, then the same of low pieces (in place of s_uc, 1 KB more:
-    // everything behind it moves by GR_EXTRA floats), and every wave has a row of UP pieces: [WPB][2][128 fp16] behind the tiles
-    constexpr int GR_ROW = 136;                            // fp16 per tile row: 128 + 8 pad (272 B)
-    constexpr int GR_EXTRA = GRID ? (2 * 64 * GR_ROW / 2 - 64 * US) : 0;
-    if constexpr (GRID) {
-        s_a4 += GR_EXTRA;
-        s_up += GR_EXTRA;
-        s_tr += GR_EXTRA;
-    }
+    float* s_uc = s_dynh + Lds::uc;
+    float* s_a4 = s_dynh + Lds::a4;
+    float* s_up = s_dynh + Lds::up;
+    float* s_tr = s_dynh + Lds::tr;
     // (all piece storage is written and read as 32-bit words = fp16 pairs: one access type, no type punning through memory)
-    uint32_t* s_uch = reinterpret_cast<uint32_t*>(s_dynh);            // [64][GR_ROW / 2]
-    uint32_t* s_ucl = s_uch + 64 * (GR_ROW / 2);
-    uint32_t* s_upp = reinterpret_cast<uint32_t*>(s_tr + WPB * 64 * PF_TS);  // [WPB][2][64]
+    uint32_t* s_uch = reinterpret_cast<uint32_t*>(s_dynh + Lds::uc);
+    uint32_t* s_ucl = reinterpret_cast<uint32_t*>(s_dynh + Lds::ucl);
+    uint32_t* s_upp = reinterpret_cast<uint32_t*>(s_dynh + Lds::upp);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     // (Placing the 8 detection tiles of a frame-pair on ONE XCD - they all read that frame-pair's UP / hand tables, 265 KB, which with
@@ -138,7 +117,6 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
     xcd_logical_block(lbx, by, b);  // the detection tiles of a frame on one XCD: its UP / UC rows come from HBM once
     const int d0 = lbx * 64;
     const int d = d0 + lane, dcl = min(d, D - 1);
-    const PackedLayout P(0, 0, F);
     {
         if constexpr (!GRID) {
             const f32x4* src = reinterpret_cast<const f32x4*>(UC);
@@ -151,19 +129,11 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
                 *reinterpret_cast<f32x4*>(&s_uc[r * US + 4 * cp]) = src[((size_t)b * D + min(d0 + r, D - 1)) * (ET / 4) + c];
             }
         }
-        const f32x4* asrc = reinterpret_cast<const f32x4*>(packed + P.a4);
-#pragma unroll 2
-        for (int e = tid; e < NA4 / 4; e += 64 * WPB) reinterpret_cast<f32x4*>(s_a4)[e] = asrc[e];
+        a4_stage<F, 64 * WPB>(packed, s_a4, tid);
     }
     float hd[12];
-    float mc;  // largest |UC| of this lane's detection row (row_prep), then of the whole 64-detection tile
-    {
-        const f32x4* h = reinterpret_cast<const f32x4*>(hand_det + ((size_t)b * D + dcl) * 16);
-        const f32x4 a = h[0], c = h[1], e = h[2], g = h[3];
-        hd[0] = a[0]; hd[1] = a[1]; hd[2] = a[2]; hd[3] = a[3]; hd[4] = c[0]; hd[5] = c[1]; hd[6] = c[2];
-        hd[7] = e[0]; hd[8] = e[1]; hd[9] = e[2]; hd[10] = e[3]; hd[11] = g[0];
-        mc = g[1];
-    }
+    // largest |UC| of this lane's detection row (row_prep), then of the whole 64-detection tile
+    float mc = load_hand_det(hand_det + ((size_t)b * D + dcl) * 16, hd);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) mc = absmax_keep_nan(mc, __shfl_xor(mc, off, 64));  // a NaN / inf row maximum survives
     const float dnm = denom[(size_t)b * D + dcl], rdn = 1.0f / dnm;
@@ -243,24 +213,22 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
     const int ew_fs = reinterpret_cast<const int*>(p16)[P16_FRAG_DW + 0], ew_rc = reinterpret_cast<const int*>(p16)[P16_FRAG_DW + 1],
               ew_fd = reinterpret_cast<const int*>(p16)[P16_FRAG_DW + 2];
     __syncthreads();
-    typedef __attribute__((address_space(3))) float lfloat;
-    typedef __attribute__((address_space(3))) f32x4 lf32x4;
-    const unsigned arow_base = (unsigned)(unsigned long long)(s_a4 + (lane & 3) * 4);
-    const unsigned abias_base = (unsigned)(unsigned long long)(s_a4 + (lane & 3));
+    const A4Lane a4l(s_a4, lane);
     const f32x4 zero4 = {0, 0, 0, 0};
     const int p = lane & 15, kb = lane >> 4;
     float* my_tr = s_tr + wid * (64 * PF_TS);
 
     const int t_beg = by * TWG + (wid < 4 ? wid * TA : 4 * TA + (wid - 4) * TB);
     const int t_end = min(min(T, (by + 1) * TWG), t_beg + (wid < 4 ? TA : TB));
-    float* my_up = s_up + wid * (3 * 256);
+    float* my_up = s_up + wid * (3 * UP_SLOT);
     const bool hp_lane = lane >= ET / 4 && lane < ET / 4 + 4;
     const int up_lane = 4 * min(lane, ET / 4 - 1), hp_off = 4 * (lane - ET / 4);
+    // (one copy per kernel: as a function in pair_lane.hpp it changed this kernel's schedule)
     auto dma_up = [&](int row, int slot) {
         const size_t r = (size_t)b * T + min(row, T - 1);
         const float* src = hp_lane ? hand_prev + r * 16 + hp_off : UP + r * ET + up_lane;
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                         (__attribute__((address_space(3))) void*)(my_up + slot * 256), 16, 0, 0);
+                                         (__attribute__((address_space(3))) void*)(my_up + slot * UP_SLOT), 16, 0, 0);
     };
     if (t_beg < t_end) {
         dma_up(t_beg, 0);
@@ -269,10 +237,10 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
     for (int t = t_beg; t < t_end; ++t) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         dma_up(t + 2, (t - t_beg + 2) % 3);
-        unsigned upo = (unsigned)(unsigned long long)(my_up + ((t - t_beg) % 3) * 256);
+        unsigned upo = (unsigned)(unsigned long long)(my_up + ((t - t_beg) % 3) * UP_SLOT);
         asm volatile("" : "+v"(upo));
         const lfloat* up = (const lfloat*)(unsigned long long)upo;
-        float hp[16];
+        float hp[16];  // (read back here: through a function of pair_lane.hpp the register allocation moved)
         {
             const f32x4 h0 = *reinterpret_cast<const lf32x4*>(up + ET), h1 = *reinterpret_cast<const lf32x4*>(up + ET + 4),
                         h2 = *reinterpret_cast<const lf32x4*>(up + ET + 8), h3 = *reinterpret_cast<const lf32x4*>(up + ET + 12);
@@ -445,77 +413,43 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
             store(3, fsB, rcB, fdB);
         }
         // ---- lane = pair from here on: descale + bias, layers 3-4, hand residual, combine (as pair_mfma4_kernel) ----
-        unsigned ao = arow_base, bo = abias_base;
-        asm volatile("" : "+v"(ao), "+v"(bo));
-        const lfloat* arow = (const lfloat*)(unsigned long long)ao;
-        const lfloat* abias = (const lfloat*)(unsigned long long)bo;
-        (void)abias;
+        const lfloat *arow, *abias;
+        a4l.per_track(arow, abias);
         // exact descaling: one exponent per track (default form) or one per MLP and workgroup (GRID)
         const float i_rc = __builtin_ldexpf(1.0f, -((GRID ? ge[1] : e1) + ew_rc)), i_fs = __builtin_ldexpf(1.0f, -((GRID ? ge[0] : e1) + ew_fs)),
                     i_fd = __builtin_ldexpf(1.0f, -((GRID ? ge[2] : e1) + ew_fd));
         f32x4 a_rc2[4], a_fs2[4], a_fd2[2];
         {
             const float* mine = my_tr + lane * PF_TS;
-            // the layer-2 biases sit behind the 4x4x1 operands of their layers in the LDS table ([ob][i], A4h<..>::BIAS)
-            const float* b_rc = s_a4 + A4h<F, L_RC2>::OFF + A4h<F, L_RC2>::BIAS;
-            const float* b_fs = s_a4 + A4h<F, L_FS2>::OFF + A4h<F, L_FS2>::BIAS;
-            const float* b_fd = s_a4 + A4h<F, L_FD2>::OFF + A4h<F, L_FD2>::BIAS;
-            // descale + bias as packed fmas (two values per 5-cycle slot instead of one per 6), ReLU right behind them
-            auto fma4 = [&](const f32x4& v, float sc, const f32x4& bb) {
-                const f32x2 s2 = {sc, sc};
-                const f32x2 lo = __builtin_elementwise_fma(f32x2{v[0], v[1]}, s2, f32x2{bb[0], bb[1]});
-                const f32x2 hi = __builtin_elementwise_fma(f32x2{v[2], v[3]}, s2, f32x2{bb[2], bb[3]});
-                // (fmaxf, not the NaN-propagating relu_nan of the other kernels: non-finite inputs never get here - finite_bound above -
-                // and v_maximum3_f32 in this loop measured 1 - 3 % of the kernel: 4.39 - 4.43 -> 4.45 - 4.56 ms)
-                return f32x4{fmaxf(lo[0], 0.0f), fmaxf(lo[1], 0.0f), fmaxf(hi[0], 0.0f), fmaxf(hi[1], 0.0f)};
-            };
+            // the layer-2 biases sit behind the 4x4x1 operands of their layers in the LDS table ([ob][i], A4<..>::BIAS)
+            const float* b_rc = s_a4 + A4<F, L_RC2>::OFF + A4<F, L_RC2>::BIAS;
+            const float* b_fs = s_a4 + A4<F, L_FS2>::OFF + A4<F, L_FS2>::BIAS;
+            const float* b_fd = s_a4 + A4<F, L_FD2>::OFF + A4<F, L_FD2>::BIAS;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                a_rc2[g] = fma4(*reinterpret_cast<const f32x4*>(mine + 4 * g), i_rc, *reinterpret_cast<const f32x4*>(b_rc + 4 * g));
-                a_fs2[g] = fma4(*reinterpret_cast<const f32x4*>(mine + 16 + 4 * g), i_fs, *reinterpret_cast<const f32x4*>(b_fs + 4 * g));
+                a_rc2[g] = a4_descale_relu(*reinterpret_cast<const f32x4*>(mine + 4 * g), i_rc, *reinterpret_cast<const f32x4*>(b_rc + 4 * g));
+                a_fs2[g] = a4_descale_relu(*reinterpret_cast<const f32x4*>(mine + 16 + 4 * g), i_fs, *reinterpret_cast<const f32x4*>(b_fs + 4 * g));
             }
 #pragma unroll
             for (int g = 0; g < 2; ++g)
-                a_fd2[g] = fma4(*reinterpret_cast<const f32x4*>(mine + 32 + 4 * g), i_fd, *reinterpret_cast<const f32x4*>(b_fd + 4 * g));
+                a_fd2[g] = a4_descale_relu(*reinterpret_cast<const f32x4*>(mine + 32 + 4 * g), i_fd, *reinterpret_cast<const f32x4*>(b_fd + 4 * g));
         }
         // All forty ReLUs of the layer-2 outputs are done before the first MFMA of layers 3-4 (the empty asm pins them there): a VALU
         // result read by the MFMA right behind it costs two wait states, and the compiler had put one v_max + s_nop 1 in front of
         // every 4x4x1.  With the third layers interleaved below: 53 -> 36 s_nop per track, pair kernel 4.73 - 4.95 -> 4.56 - 4.62 ms.
         asm volatile("" : "+v"(a_rc2[0]), "+v"(a_rc2[1]), "+v"(a_rc2[2]), "+v"(a_rc2[3]), "+v"(a_fs2[0]), "+v"(a_fs2[1]), "+v"(a_fs2[2]),
                      "+v"(a_fs2[3]), "+v"(a_fd2[0]), "+v"(a_fd2[1]));
-        auto init = [&](auto tag, f32x4* acc) {
-            using AL = decltype(tag);
-#pragma unroll
-            for (int ob = 0; ob < AL::NOB; ++ob) acc[ob] = MFMA4(abias[AL::OFF + AL::BIAS + ob * 4], 1.0f, zero4);
-        };
-        auto layer = [&](auto tag, const f32x4* in, f32x4* acc, auto relu_done) {
-            using AL = decltype(tag);
-            init(tag, acc);
-#pragma unroll
-            for (int kg = 0; kg < AL::KG; ++kg) {
-                f32x4 a4[AL::NOB];
-#pragma unroll
-                for (int ob = 0; ob < AL::NOB; ++ob) a4[ob] = *reinterpret_cast<const lf32x4*>(arow + AL::OFF + (ob * AL::KG + kg) * 16);
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                    if (4 * kg + kk < AL::KIN) {
-                        const float h = decltype(relu_done)::value ? in[kg][kk] : fmaxf(in[kg][kk], 0.0f);
-#pragma unroll
-                        for (int ob = 0; ob < AL::NOB; ++ob) acc[ob] = MFMA4(a4[ob][kk], h, acc[ob]);
-                    }
-                }
-            }
-        };
-        f32x4 a_rc3[A4h<F, L_RC3>::NOB], a_fs3[A4h<F, L_FS3>::NOB], a_fs4[A4h<F, L_FS4>::NOB], a_fd3[A4h<F, L_FD3>::NOB];
+        f32x4 a_rc3[A4<F, L_RC3>::NOB], a_fs3[A4<F, L_FS3>::NOB], a_fs4[A4<F, L_FS4>::NOB], a_fd3[A4<F, L_FD3>::NOB];
         {
             // the three third layers side by side: every accumulator is touched once per round, so no 4x4x1 waits for the one before it
-            using RC = A4h<F, L_RC3>;
-            using FS = A4h<F, L_FS3>;
-            using FD = A4h<F, L_FD3>;
+            // (one copy per fp16 kernel: a function shared by the two changed both schedules)
+            using RC = A4<F, L_RC3>;
+            using FS = A4<F, L_FS3>;
+            using FD = A4<F, L_FD3>;
             static_assert(RC::NOB == 1 && FS::NOB == 2 && FD::NOB == 1 && RC::KG == 4 && FS::KG == 4 && FD::KG == 2, "F = 256");
-            init(RC{}, a_rc3);
-            init(FS{}, a_fs3);
-            init(FD{}, a_fd3);
+            a4_init<RC>(abias, a_rc3);
+            a4_init<FS>(abias, a_fs3);
+            a4_init<FD>(abias, a_fd3);
 #pragma unroll
             for (int kg = 0; kg < 4; ++kg) {
                 const f32x4 w_rc = *reinterpret_cast<const lf32x4*>(arow + RC::OFF + kg * 16);
@@ -532,21 +466,13 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
                 }
             }
         }
-        layer(A4h<F, L_FS4>{}, a_fs3, a_fs4, std::false_type{});
+        a4_layer<A4<F, L_FS4>, A4_RELU_FMAX>(arow, abias, a_fs3, a_fs4);
 
         // ---- hand-designed residual (shasta.py:277-283) ----
         const float dist = hand_dist(hp, hd, dnm, rdn);
-        // ---- combine (shasta.py:316-319) ----
-        const float res = (a_rc3[0][0] * a_fd3[0][0] + a_rc3[0][1] * dist) + a_rc3[0][2] * a_fs4[0][0];
+        const float res = pair_combine(a_rc3[0], a_fd3[0][0], dist, a_fs4[0][0]);
         if (d < D) residual[((size_t)b * T + t) * ld + d] = finite_bound ? res : __builtin_nanf("");
     }
-}
-
-static size_t pair_f16_lds_bytes(int wpb, bool grid) {
-    constexpr PairDims dm(256);
-    const size_t base = ((size_t)64 * (dm.ET + 4) + ((a4_total(256) + 3) & ~3) + (size_t)wpb * 3 * 256 + (size_t)wpb * 64 * PF_TS) * sizeof(float);
-    // GRID: the fp16 piece tile is 1 KB larger than the fp32 tile, + 512 bytes of UP pieces per wave
-    return base + (grid ? (size_t)(2 * 64 * 136 * 2 - 64 * (dm.ET + 4) * 4) + (size_t)wpb * 512 : 0);
 }
 
 int launch_pair_f16(const float* packed, const float* p16, const float* UP, const float* UC, const float* hand_prev,
@@ -572,7 +498,7 @@ int launch_pair_f16(const float* packed, const float* p16, const float* UP, cons
         ta = (per_simd * 1000 + (1000 + 615) / 2) / (1000 + 615);  // to nearest; 615 tracks of a late wave per 1000 of an early one
         tb = per_simd - ta;
     }
-    const size_t lds = pair_f16_lds_bytes(wpb, grid);
+    const size_t lds = grid ? PairF16Lds<wpb, true>::bytes : PairF16Lds<wpb, false>::bytes;
     dim3 grd(cdiv(D, 64), cdiv(T, twg), B);
     if (grid) {
         (void)hipFuncSetAttribute((const void*)pair_f16_kernel<wpb, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

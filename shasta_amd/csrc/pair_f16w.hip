@@ -30,14 +30,10 @@
 // ~85 % of the time at the ~1.7 GHz the power cap leaves under this load - removing vector work (the in-place UP scaling below:
 // -68 instructions) moved the time by 1.6 %.
 #include "stages.hpp"
-#include "pair_layout.hpp"
+#include "pair_lane.hpp"
 #include "pieces.hpp"
 
-#include <type_traits>
-
 namespace shasta {
-
-#define MFMA4W(a, b, c) __builtin_amdgcn_mfma_f32_4x4x1f32((a), (b), (c), 0, 0, 0)
 
 template <int F>
 struct PW {
@@ -59,12 +55,6 @@ struct PW {
 constexpr int P16W_MAX_DW = 2 * 16 * 64 * 4 + 4;
 static_assert(PW<320>::FRAG_DW + 4 <= P16W_MAX_DW && PW<256>::FRAG_DW + 4 <= P16W_MAX_DW, "PackedLayout::p16w");
 
-template <int F, int L>
-struct A4w {
-    static constexpr LayerDesc D = layer_desc(F, L);
-    static constexpr int NOB = a4_nob(F, L), KG = a4_kg(F, L), OFF = a4_offset(F, L), KIN = D.kin, BIAS = NOB * KG * 16;
-};
-
 // (the asm helpers of pieces.hpp and w_mul2 below: hazard rule of pieces.hpp)
 __device__ __forceinline__ f32x2 w_mul2(f32x2 a, f32x2 c) {  // (the compiler splits an f32x2 product of an asm result into two v_mul_f32)
     f32x2 r;
@@ -77,12 +67,7 @@ __device__ __forceinline__ f32x2 w_mul2(f32x2 a, f32x2 c) {  // (the compiler sp
 // block 1 is fuse_shape.2 row m (m < H2, columns [0, H1)) or fuse_det.2 row m - H2 (m < H2 + 8, columns [H1 + R1, ET)) and row m of
 // block 2 is res_coeff.2 row m (m < R2, columns [H1, H1 + R1)); zero elsewhere.  High pieces of all fragments, then low pieces, then
 // the three exponents (fs, rc, fd).
-struct PairF16WPackArgs {
-    const float* w_fs2;  // fuse_shape.2.weight (H2, H1)
-    const float* w_rc2;  // res_coeff.2.weight (R2, R1)
-    const float* w_fd2;  // fuse_det.2.weight (8, 32)
-    uint32_t* out;
-};
+struct PairF16WPackArgs : PairF16PackArgs {};  // (a type of its own: its name is part of the kernel's symbol)
 
 template <int F>
 __global__ __launch_bounds__(256) void pair_f16w_pack_kernel(PairF16WPackArgs a) {
@@ -111,34 +96,29 @@ __global__ __launch_bounds__(256) void pair_f16w_pack_kernel(PairF16WPackArgs a)
             }
             v[j] = x;
         }
-        u32x4 hi, lo;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const _Float16 h0 = (_Float16)v[2 * j], h1 = (_Float16)v[2 * j + 1];
-            const f16x2 hh = {h0, h1};
-            hi[j] = __builtin_bit_cast(uint32_t, hh);
-            lo[j] = cvt_f16x2(v[2 * j] - (float)h0, v[2 * j + 1] - (float)h1);
-        }
-        reinterpret_cast<u32x4*>(a.out)[(0 * W::NFRAG + frag) * 64 + lane] = hi;
-        reinterpret_cast<u32x4*>(a.out)[(1 * W::NFRAG + frag) * 64 + lane] = lo;
+        store_weight_pieces(v, a.out, W::NFRAG, frag, lane);
     }
 }
 
 bool pair_f16w_serves(int F) { return F == 320; }
 
 int pair_f16w_pack(const shasta_weights* w, float* out, hipStream_t st) {
-    PairF16WPackArgs a;
-    a.w_fs2 = w->fuse_shape[1].weight;
-    a.w_rc2 = w->res_coeff[1].weight;
-    a.w_fd2 = w->fuse_det[1].weight;
-    a.out = reinterpret_cast<uint32_t*>(out);
-    hipLaunchKernelGGL(pair_f16w_pack_kernel<320>, dim3(1), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(pair_f16w_pack_kernel<320>, dim3(1), dim3(256), 0, st, PairF16WPackArgs{pair_f16_pack_args(w, out)});
     return check_launch("pair_f16w_pack");
 }
 
 // ---- the kernel -------------------------------------------------------------------------------------------------------------
 constexpr int PWK_WPB = 4;       // waves per workgroup (two workgroups per CU: two waves per SIMD)
-constexpr int PWK_SLOT = 256;    // floats per UP row slot (a row = ET + 16 hand floats; one 1 KB LDS-DMA per row)
+
+// dynamic LDS of pair_f16w_kernel (float offsets): the kernel carves it, the launcher sizes it
+template <int F>
+struct PairF16wLds {
+    static constexpr int a4 = 0;                              // [a4_total(F)] 4x4x1 operand table (layers 3-4 and the layer-2 biases)
+    static constexpr int up = a4 + pad4(a4_total(F));         // [WPB][3 steps][2 rows][UP_SLOT]
+    static constexpr int w = up + PWK_WPB * 6 * UP_SLOT;      // [piece][fragment][lane] second-layer weight pieces (u32x4)
+    static constexpr size_t bytes = (size_t)(w + PW<F>::FRAG_DW) * sizeof(float);
+};
+static_assert(PairF16wLds<320>::bytes == 56928, "the size the launcher spelt out before");
 
 template <int F>
 __global__ __launch_bounds__(64 * PWK_WPB) __attribute__((amdgpu_waves_per_eu(2, 2))) void pair_f16w_kernel(const float* __restrict__ packed, const uint32_t* __restrict__ p16,
@@ -148,11 +128,11 @@ __global__ __launch_bounds__(64 * PWK_WPB) __attribute__((amdgpu_waves_per_eu(2,
                                                                int D, int ld, int TWG) {
     using W = PW<F>;
     constexpr int ET = W::ET, NKS = W::NKS, NFRAG = W::NFRAG;
-    constexpr int NA4 = a4_total(F);
+    using Lds = PairF16wLds<F>;
     extern __shared__ __attribute__((aligned(16))) float s_dynw[];
-    float* s_a4 = s_dynw;                          // [NA4] 4x4x1 operand table (layers 3-4 and the layer-2 biases)
-    float* s_up = s_dynw + ((NA4 + 3) & ~3);       // [WPB][3 steps][2 rows][PWK_SLOT]
-    u32x4* s_w = reinterpret_cast<u32x4*>(s_up + PWK_WPB * 6 * PWK_SLOT);  // [piece][fragment][lane] second-layer weight pieces
+    float* s_a4 = s_dynw + Lds::a4;
+    float* s_up = s_dynw + Lds::up;
+    u32x4* s_w = reinterpret_cast<u32x4*>(s_dynw + Lds::w);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     int lbx, by, b;
@@ -160,12 +140,7 @@ __global__ __launch_bounds__(64 * PWK_WPB) __attribute__((amdgpu_waves_per_eu(2,
     const int d0 = lbx * 32;
     const int n = lane & 31, kb = lane >> 5;
     const int d = d0 + n, dcl = min(d, D - 1);
-    const PackedLayout P(0, 0, F);
-    {
-        const f32x4* asrc = reinterpret_cast<const f32x4*>(packed + P.a4);
-#pragma unroll 2
-        for (int e = tid; e < NA4 / 4; e += 64 * PWK_WPB) reinterpret_cast<f32x4*>(s_a4)[e] = asrc[e];
-    }
+    a4_stage<F, 64 * PWK_WPB>(packed, s_a4, tid);
     // this lane's UC values, for the whole kernel: columns 16 ks + 8 kb .. + 7 of detection n
     f32x4 uc[NKS][2];
     {
@@ -177,14 +152,8 @@ __global__ __launch_bounds__(64 * PWK_WPB) __attribute__((amdgpu_waves_per_eu(2,
         }
     }
     float hd[12];
-    float mc;  // largest |UC| of this lane's detection row (row_prep), then of the whole 32-detection tile
-    {
-        const f32x4* h = reinterpret_cast<const f32x4*>(hand_det + ((size_t)b * D + dcl) * 16);
-        const f32x4 a = h[0], c = h[1], e = h[2], g = h[3];
-        hd[0] = a[0]; hd[1] = a[1]; hd[2] = a[2]; hd[3] = a[3]; hd[4] = c[0]; hd[5] = c[1]; hd[6] = c[2];
-        hd[7] = e[0]; hd[8] = e[1]; hd[9] = e[2]; hd[10] = e[3]; hd[11] = g[0];
-        mc = g[1];
-    }
+    // largest |UC| of this lane's detection row (row_prep), then of the whole 32-detection tile
+    float mc = load_hand_det(hand_det + ((size_t)b * D + dcl) * 16, hd);
 #pragma unroll
     for (int off = 16; off > 0; off >>= 1) mc = absmax_keep_nan(mc, __shfl_xor(mc, off, 64));  // (both halves hold the same 32 rows)
     const float dnm = denom[(size_t)b * D + dcl], rdn = 1.0f / dnm;
@@ -194,10 +163,7 @@ __global__ __launch_bounds__(64 * PWK_WPB) __attribute__((amdgpu_waves_per_eu(2,
     const int ew_fs = reinterpret_cast<const int*>(p16)[W::FRAG_DW + 0], ew_rc = reinterpret_cast<const int*>(p16)[W::FRAG_DW + 1],
               ew_fd = reinterpret_cast<const int*>(p16)[W::FRAG_DW + 2];
     __syncthreads();
-    typedef __attribute__((address_space(3))) float lfloat;
-    typedef __attribute__((address_space(3))) f32x4 lf32x4;
-    const unsigned arow_base = (unsigned)(unsigned long long)(s_a4 + (lane & 3) * 4);
-    const unsigned abias_base = (unsigned)(unsigned long long)(s_a4 + (lane & 3));
+    const A4Lane a4l(s_a4, lane);
     const f32x4 zero4 = {0, 0, 0, 0};
     const f32x16 zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
@@ -205,14 +171,15 @@ __global__ __launch_bounds__(64 * PWK_WPB) __attribute__((amdgpu_waves_per_eu(2,
     const int tw = TWG / PWK_WPB;
     const int t_beg = by * TWG + wid * tw;
     const int t_end = min(min(T, (by + 1) * TWG), t_beg + tw);
-    float* my_up = s_up + wid * (6 * PWK_SLOT);
+    float* my_up = s_up + wid * (6 * UP_SLOT);
     const bool hp_lane = lane >= ET / 4 && lane < ET / 4 + 4;
     const int up_lane = 4 * min(lane, ET / 4 - 1), hp_off = 4 * (lane - ET / 4);
+    // (one copy per kernel: as a function in pair_lane.hpp it changed the other two kernels' schedules)
     auto dma_up = [&](int row, int slot) __attribute__((always_inline)) {
         const size_t r = (size_t)b * T + min(row, T - 1);
         const float* src = hp_lane ? hand_prev + r * 16 + hp_off : UP + r * ET + up_lane;
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                         (__attribute__((address_space(3))) void*)(my_up + slot * PWK_SLOT), 16, 0, 0);
+                                         (__attribute__((address_space(3))) void*)(my_up + slot * UP_SLOT), 16, 0, 0);
     };
     if (t_beg < t_end) {
         dma_up(t_beg, 0);
@@ -226,10 +193,10 @@ __global__ __launch_bounds__(64 * PWK_WPB) __attribute__((amdgpu_waves_per_eu(2,
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         dma_up(t + 4, ((step + 2) % 3) * 2);
         dma_up(t + 5, ((step + 2) % 3) * 2 + 1);
-        unsigned upo = (unsigned)(unsigned long long)(my_up + (step % 3) * 2 * PWK_SLOT);
+        unsigned upo = (unsigned)(unsigned long long)(my_up + (step % 3) * 2 * UP_SLOT);
         asm volatile("" : "+v"(upo));
         const lfloat* upA = (const lfloat*)(unsigned long long)upo;
-        const lfloat* upB = upA + PWK_SLOT;
+        const lfloat* upB = upA + UP_SLOT;
         // the two tracks' scales (uniform): every h1 of a track and this tile is at most max |UP[t]| + max |UC| (pair_f16.hip)
         const float boundA = upA[ET + 13] + mc, boundB = upB[ET + 13] + mc;
         const int e1A = range_exponent_bits(__float_as_uint(boundA)), e1B = range_exponent_bits(__float_as_uint(boundB));
@@ -241,7 +208,7 @@ __global__ __launch_bounds__(64 * PWK_WPB) __attribute__((amdgpu_waves_per_eu(2,
             typedef __attribute__((address_space(3))) f32x4 wlf32x4;
             const int q = 4 * min(lane, ET / 4 - 1);
             wlf32x4* pa = (wlf32x4*)(unsigned long long)(upo + 4 * q);
-            wlf32x4* pb = (wlf32x4*)(unsigned long long)(upo + 4 * (PWK_SLOT + q));
+            wlf32x4* pb = (wlf32x4*)(unsigned long long)(upo + 4 * (UP_SLOT + q));
             const f32x4 va = *pa, vb = *pb;
             const f32x2 a0 = w_mul2(f32x2{va[0], va[1]}, cs2A), a1 = w_mul2(f32x2{va[2], va[3]}, cs2A);
             const f32x2 b0 = w_mul2(f32x2{vb[0], vb[1]}, cs2B), b1 = w_mul2(f32x2{vb[2], vb[3]}, cs2B);
@@ -328,8 +295,8 @@ __global__ __launch_bounds__(64 * PWK_WPB) __attribute__((amdgpu_waves_per_eu(2,
             }
         // ---- lane = pair from here on ----------------------------------------------------------------------------------------
         const int my_t = t + kb;
-        const lfloat* upL = upA + kb * PWK_SLOT;
-        float hp[16];
+        const lfloat* upL = upA + kb * UP_SLOT;
+        float hp[16];  // (read back here: through a function of pair_lane.hpp the register allocation moved)
         {
             const f32x4 h0 = *reinterpret_cast<const lf32x4*>(upL + ET), h1 = *reinterpret_cast<const lf32x4*>(upL + ET + 4),
                         h2 = *reinterpret_cast<const lf32x4*>(upL + ET + 8), h3 = *reinterpret_cast<const lf32x4*>(upL + ET + 12);
@@ -344,63 +311,33 @@ __global__ __launch_bounds__(64 * PWK_WPB) __attribute__((amdgpu_waves_per_eu(2,
         const float bound = kb ? boundB : boundA;
         const bool finite_bound = bound < INFINITY;  // false for NaN and +inf (pair_f16.hip)
         const int e1 = kb ? e1B : e1A;
-        unsigned ao = arow_base, bo = abias_base;
-        asm volatile("" : "+v"(ao), "+v"(bo));
-        const lfloat* arow = (const lfloat*)(unsigned long long)ao;
-        const lfloat* abias = (const lfloat*)(unsigned long long)bo;
+        const lfloat *arow, *abias;
+        a4l.per_track(arow, abias);
         const float i_rc = __builtin_ldexpf(1.0f, -(e1 + ew_rc)), i_fs = __builtin_ldexpf(1.0f, -(e1 + ew_fs)), i_fd = __builtin_ldexpf(1.0f, -(e1 + ew_fd));
         constexpr int NQ_FS = W::H2 / 4, NQ_RC = (W::R2 + 3) / 4;
         f32x4 a_fs2[NQ_FS], a_rc2[NQ_RC], a_fd2[2];
         {
-            const float* b_rc = s_a4 + A4w<F, L_RC2>::OFF + A4w<F, L_RC2>::BIAS;
-            const float* b_fs = s_a4 + A4w<F, L_FS2>::OFF + A4w<F, L_FS2>::BIAS;
-            const float* b_fd = s_a4 + A4w<F, L_FD2>::OFF + A4w<F, L_FD2>::BIAS;
-            auto fma4 = [&](const f32x4& v, float sc, const f32x4& bb) __attribute__((always_inline)) {
-                const f32x2 s2 = {sc, sc};
-                const f32x2 lo = __builtin_elementwise_fma(f32x2{v[0], v[1]}, s2, f32x2{bb[0], bb[1]});
-                const f32x2 hi = __builtin_elementwise_fma(f32x2{v[2], v[3]}, s2, f32x2{bb[2], bb[3]});
-                return f32x4{fmaxf(lo[0], 0.0f), fmaxf(lo[1], 0.0f), fmaxf(hi[0], 0.0f), fmaxf(hi[1], 0.0f)};
-            };
+            const float* b_rc = s_a4 + A4<F, L_RC2>::OFF + A4<F, L_RC2>::BIAS;
+            const float* b_fs = s_a4 + A4<F, L_FS2>::OFF + A4<F, L_FS2>::BIAS;
+            const float* b_fd = s_a4 + A4<F, L_FD2>::OFF + A4<F, L_FD2>::BIAS;
 #pragma unroll
-            for (int g = 0; g < NQ_FS; ++g) a_fs2[g] = fma4(q1[g], i_fs, *reinterpret_cast<const f32x4*>(b_fs + 4 * g));
+            for (int g = 0; g < NQ_FS; ++g) a_fs2[g] = a4_descale_relu(q1[g], i_fs, *reinterpret_cast<const f32x4*>(b_fs + 4 * g));
 #pragma unroll
-            for (int g = 0; g < 2; ++g) a_fd2[g] = fma4(q1[NQ_FS + g], i_fd, *reinterpret_cast<const f32x4*>(b_fd + 4 * g));
+            for (int g = 0; g < 2; ++g) a_fd2[g] = a4_descale_relu(q1[NQ_FS + g], i_fd, *reinterpret_cast<const f32x4*>(b_fd + 4 * g));
 #pragma unroll
-            for (int g = 0; g < NQ_RC; ++g) a_rc2[g] = fma4(q2[g], i_rc, *reinterpret_cast<const f32x4*>(b_rc + 4 * g));
+            for (int g = 0; g < NQ_RC; ++g) a_rc2[g] = a4_descale_relu(q2[g], i_rc, *reinterpret_cast<const f32x4*>(b_rc + 4 * g));
         }
-        auto init = [&](auto tag, f32x4* acc) __attribute__((always_inline)) {
-            using AL = decltype(tag);
-#pragma unroll
-            for (int ob = 0; ob < AL::NOB; ++ob) acc[ob] = MFMA4W(abias[AL::OFF + AL::BIAS + ob * 4], 1.0f, zero4);
-        };
-        auto layer = [&](auto tag, const f32x4* in, f32x4* acc, auto relu_done) __attribute__((always_inline)) {
-            using AL = decltype(tag);
-            init(tag, acc);
-#pragma unroll
-            for (int kg = 0; kg < AL::KG; ++kg) {
-                f32x4 a4[AL::NOB];
-#pragma unroll
-                for (int ob = 0; ob < AL::NOB; ++ob) a4[ob] = *reinterpret_cast<const lf32x4*>(arow + AL::OFF + (ob * AL::KG + kg) * 16);
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                    if (4 * kg + kk < AL::KIN) {
-                        const float h = decltype(relu_done)::value ? in[kg][kk] : fmaxf(in[kg][kk], 0.0f);
-#pragma unroll
-                        for (int ob = 0; ob < AL::NOB; ++ob) acc[ob] = MFMA4W(a4[ob][kk], h, acc[ob]);
-                    }
-                }
-            }
-        };
-        f32x4 a_rc3[A4w<F, L_RC3>::NOB], a_fs3[A4w<F, L_FS3>::NOB], a_fs4[A4w<F, L_FS4>::NOB], a_fd3[A4w<F, L_FD3>::NOB];
+        f32x4 a_rc3[A4<F, L_RC3>::NOB], a_fs3[A4<F, L_FS3>::NOB], a_fs4[A4<F, L_FS4>::NOB], a_fd3[A4<F, L_FD3>::NOB];
         {
             // the three third layers side by side: every accumulator is touched once per round, so no 4x4x1 waits for the one before it
-            using FS = A4w<F, L_FS3>;
-            using RC = A4w<F, L_RC3>;
-            using FD = A4w<F, L_FD3>;
+            // (one copy per fp16 kernel: a function shared by the two changed both schedules)
+            using FS = A4<F, L_FS3>;
+            using RC = A4<F, L_RC3>;
+            using FD = A4<F, L_FD3>;
             static_assert(RC::NOB == 1 && FD::NOB == 1 && FD::KG == 2, "third layers: res_coeff -> 3, fuse_det -> 1");
-            init(FS{}, a_fs3);
-            init(RC{}, a_rc3);
-            init(FD{}, a_fd3);
+            a4_init<FS>(abias, a_fs3);
+            a4_init<RC>(abias, a_rc3);
+            a4_init<FD>(abias, a_fd3);
             constexpr int KGM = FS::KG > RC::KG ? FS::KG : RC::KG;
 #pragma unroll
             for (int kg = 0; kg < KGM; ++kg) {
@@ -414,22 +351,18 @@ __global__ __launch_bounds__(64 * PWK_WPB) __attribute__((amdgpu_waves_per_eu(2,
                 for (int kk = 0; kk < 4; ++kk) {
                     if (kg < FS::KG && 4 * kg + kk < FS::KIN)
 #pragma unroll
-                        for (int ob = 0; ob < FS::NOB; ++ob) a_fs3[ob] = MFMA4W(w_fs[ob][kk], a_fs2[kg][kk], a_fs3[ob]);
-                    if (kg < RC::KG && 4 * kg + kk < RC::KIN) a_rc3[0] = MFMA4W(w_rc[kk], a_rc2[kg][kk], a_rc3[0]);
-                    if (kg < FD::KG) a_fd3[0] = MFMA4W(w_fd[kk], a_fd2[kg][kk], a_fd3[0]);
+                        for (int ob = 0; ob < FS::NOB; ++ob) a_fs3[ob] = MFMA4(w_fs[ob][kk], a_fs2[kg][kk], a_fs3[ob]);
+                    if (kg < RC::KG && 4 * kg + kk < RC::KIN) a_rc3[0] = MFMA4(w_rc[kk], a_rc2[kg][kk], a_rc3[0]);
+                    if (kg < FD::KG) a_fd3[0] = MFMA4(w_fd[kk], a_fd2[kg][kk], a_fd3[0]);
                 }
             }
         }
-        layer(A4w<F, L_FS4>{}, a_fs3, a_fs4, std::false_type{});
-        // ---- hand-designed residual (shasta.py:277-283) and combine (shasta.py:316-319) ----
+        a4_layer<A4<F, L_FS4>, A4_RELU_FMAX>(arow, abias, a_fs3, a_fs4);
+        // ---- hand-designed residual (shasta.py:277-283) and combine ----
         const float dist = hand_dist(hp, hd, dnm, rdn);
-        const float res = (a_rc3[0][0] * a_fd3[0][0] + a_rc3[0][1] * dist) + a_rc3[0][2] * a_fs4[0][0];
+        const float res = pair_combine(a_rc3[0], a_fd3[0][0], dist, a_fs4[0][0]);
         if (d < D && my_t < t_end) residual[((size_t)b * T + my_t) * ld + d] = finite_bound ? res : __builtin_nanf("");
     }
-}
-
-static size_t pair_f16w_lds_bytes(int F) {
-    return ((size_t)((a4_total(F) + 3) & ~3) + (size_t)PWK_WPB * 6 * PWK_SLOT) * sizeof(float) + (size_t)PW<320>::FRAG_DW * 4;
 }
 
 int launch_pair_f16w(const float* packed, const float* p16, const float* UP, const float* UC, const float* hand_prev,
@@ -445,7 +378,7 @@ int launch_pair_f16w(const float* packed, const float* p16, const float* UP, con
     while ((long)B * cdiv(D, 32) * ny < 512 && cdiv(T, unit * ny * 2) >= 2) ny *= 2;
     while ((long)B * cdiv(D, 32) * ny < 256 && cdiv(T, unit * ny * 2) >= 1) ny *= 2;
     const int twg = cdiv(cdiv(T, ny), unit) * unit;
-    const size_t lds = pair_f16w_lds_bytes(F);
+    constexpr size_t lds = PairF16wLds<320>::bytes;
     dim3 grd(cdiv(D, 32), cdiv(T, twg), B);
     if (hipFuncSetAttribute((const void*)pair_f16w_kernel<320>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
         (void)hipGetLastError();
