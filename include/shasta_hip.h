@@ -517,6 +517,42 @@ int shasta_track_merged_f64(const double* det_xy, const double* det_vel, const i
                             const double* cls_alpha, const double* cls_beta, int max_age, int plain, int32_t* out_status,
                             int32_t* out_id, double* out_ref, int32_t* out_err, shasta_stream_t stream);
 
+/* The same launch with the Hungarian assignment (`hungarian=True` of both reference trackers, pub_tracker.py:103-128 /
+ * pub_tracker_merged.py:131-150) instead of the greedy one: per group - merged: one tracking class, plain: all of them - scipy's
+ * linear_sum_assignment (shasta_lsap_f64's algorithm) over the group's detections in file order x its tracks in list order, cost =
+ * the float32 centre distance, 1e18 for a pair beyond the gate or of two classes, computed on the fly (no matrix in memory; solver
+ * state in the workgroup's LDS, 158 048 bytes in all).  The solver pairs min(detections, tracks) pairs; a pair whose cost exceeds
+ * 1e16 is no match: its detection counts as unmatched BEHIND the never-paired ones (out_status 3 instead of 2: ids are issued and
+ * result rows emitted in that order), its track is dropped without coasting.  Everything else as shasta_track_merged_f64. */
+int shasta_track_merged_lsap_f64(const double* det_xy, const double* det_vel, const int32_t* det_cls, const double* det_score,
+                                 const double* det_ref, const int32_t* det_flags, const int32_t* frame_off, const double* frame_lag,
+                                 const int32_t* n_frames, int scenes, int Fmax, int n_cls, const float* cls_gate, const int32_t* cls_ref,
+                                 const double* cls_alpha, const double* cls_beta, int max_age, int plain, int32_t* out_status,
+                                 int32_t* out_id, double* out_ref, int32_t* out_err, shasta_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Batched linear sum assignment (Hungarian), float64, on the device
+ * replaces scipy.optimize.linear_sum_assignment behind tools/nusc_shasta/pub_tracker.py:105 (`hungarian=True`) and
+ * mot_3d/association.py `mode='bipartite'`.  Same algorithm as scipy's rectangular_lsap (shortest augmenting paths, transposed when
+ * there are more rows than columns), same order of the float64 additions, same tie rule: the assignment - not only its cost - equals
+ * scipy's, also where 1e18 entries swallow the small costs.  One wavefront per problem.
+ *  cost (P,Nmax,Mmax) float64, n / m (P,) int32 valid rows / columns of every problem (device); cells outside n x m are never read
+ *  col_of_row (P,Nmax) int32: the column assigned to every row, -1 = none (rows >= n, the surplus rows of a tall problem, any
+ *  problem whose status is not 0);  the pairs in ascending row order are scipy's (row_ind, col_ind)
+ *  status (P,) int32, written on the device without a host synchronisation: 0 ok (also n == 0 or m == 0: no pairs), 1 = a cost
+ *  inside n x m is NaN or -inf (scipy raises ValueError there) or n / m exceed Nmax / Mmax, 2 = infeasible (+inf marks a forbidden
+ *  pair, as in scipy; some row has only forbidden columns left)
+ *  Nmax, Mmax <= 1024 (the solver state of a problem lives in LDS), beyond: SHASTA_E_UNSUPPORTED
+ * ------------------------------------------------------------------------------------------ */
+int shasta_lsap_f64(const double* cost, const int32_t* n, const int32_t* m, int problems, int Nmax, int Mmax,
+                    int32_t* col_of_row, int32_t* status, shasta_stream_t stream);
+/* The tracker's form (pub_tracker.py:102-106,119-126) behind shasta_center_greedy_f32's `dist` on the same stream: every cost above
+ * `clip` counts as `clip` (`dist[dist > 1e18] = 1e18`, applied while reading - the matrix is not modified), and over (P,Nmax) int32
+ * gets 1 for every row whose pair costs more than `over_above` (1e16: "paired, but no match"), 0 elsewhere - with col_of_row all the
+ * tracker's bookkeeping needs, so no matrix travels to the host. */
+int shasta_lsap_clip_f64(const double* cost, const int32_t* n, const int32_t* m, int problems, int Nmax, int Mmax, double clip,
+                         double over_above, int32_t* col_of_row, int32_t* over, int32_t* status, shasta_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Training path, backward helpers (the nn.Linear layers run on shasta_gemm_strided_f32; the first layer of each pair MLP
  * is factorised over the table rows).  Replaces what torch autograd derives from det3d/models/tracker/shasta.py:241-325 in

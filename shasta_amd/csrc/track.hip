@@ -7,7 +7,7 @@
 //                if that minimum < 1e16: match (i, j), take column j.
 // The greedy loop is sequential in i by definition; one wavefront owns one scene (no barrier: the taken-column flags live
 // in LDS words private to the wave, the argmin is a butterfly over (value, index) pairs), scenes run side by side.
-#include "common.hpp"
+#include "lsap.hpp"
 
 namespace shasta {
 
@@ -120,6 +120,10 @@ constexpr int TM_DCAP = 512;   // detections of one frame
 constexpr int TM_NCLS = 8;
 // dynamic LDS (one workgroup = one wavefront per CU): 2 track buffers x 60 B x TM_TCAP + 64 B x TM_DCAP + flags = ~130 KB
 constexpr size_t TM_LDS_BYTES = (size_t)2 * TM_TCAP * (5 * 8 + 5 * 4) + (size_t)TM_DCAP * (6 * 8 + 2 * 4 + 4 * 4) + (size_t)TM_TCAP * 4 + TM_TCAP / 32 * 4;
+// the Hungarian rule adds the solver's state (lsap.hpp; the smaller side of a problem is the row side: at most TM_DCAP rows, TM_TCAP
+// columns) and the two index lists of the group being solved: + 25 KB, 158 048 of the CU's 163 840 bytes - one workgroup per CU as before
+constexpr size_t TM_LSAP_BYTES = lsap_state_bytes(TM_DCAP, TM_TCAP) + (size_t)2 * (TM_DCAP + TM_TCAP);
+static_assert(TM_LDS_BYTES % 8 == 0 && TM_LDS_BYTES + TM_LSAP_BYTES <= 160 * 1024, "scene tracker: LDS carve-up");
 
 struct TrackMergedArgs {
     const double* det_xy;     // (D, 2) translation[:2]
@@ -131,7 +135,8 @@ struct TrackMergedArgs {
     const int* frame_off;     // (S, Fmax + 1) offsets into the detection arrays
     const double* frame_lag;  // (S, Fmax) time_lag of step_centertrack
     const int* n_frames;      // (S,)
-    int* out_status;          // (D,) 0: not in the frame's result, 1: matched to a track, 2: new track
+    int* out_status;          // (D,) 0: not in the frame's result, 1: matched to a track, 2: new track, 3 (Hungarian rule): new track of a
+                              //      detection the solver paired beyond the gate - these follow the never-paired ones
     int* out_id;              // (D,) tracking_id
     double* out_ref;          // (D,) refined ref_detection_score
     int* out_err;             // (S,) 0 ok, 1: a frame holds more than TM_DCAP detections, 2: more than TM_TCAP tracks
@@ -142,6 +147,11 @@ struct TrackMergedArgs {
     double alpha[TM_NCLS], beta[TM_NCLS];
 };
 
+// HUNG: the assignment of a group (merged: one class; plain: all tracking classes) is scipy's linear_sum_assignment over its detections
+// (rows, file order) x its tracks (columns, list order) with the cost `invalid ? 1e18 : d` - pub_tracker.py:102-104's `d + 1e18`
+// clipped to 1e18 - evaluated on the fly; a pair beyond 1e16 is no match: its detection joins the unmatched ones BEHIND the never-paired
+// ones, its track is neither matched nor coasted (pub_tracker.py:113-128).
+template <bool HUNG>
 __global__ __launch_bounds__(64) void track_merged_kernel(TrackMergedArgs a) {
     extern __shared__ __attribute__((aligned(16))) double tm_lds[];
     // carve-up: doubles first, then the 4-byte arrays
@@ -169,6 +179,9 @@ __global__ __launch_bounds__(64) void track_merged_kernel(TrackMergedArgs a) {
     int* d_near = d_match + TM_DCAP;
     int* t_near = d_near + TM_DCAP;
     unsigned* taken = reinterpret_cast<unsigned*>(t_near + TM_TCAP);
+    const LsapState ls = lsap_carve(taken + TM_TCAP / 32, TM_DCAP, TM_TCAP);  // (HUNG only: the launch grants the bytes)
+    short* g_det = reinterpret_cast<short*>(ls.SC + TM_TCAP);                  // detections / tracks of the group being solved
+    short* g_trk = g_det + TM_DCAP;
     const int s = blockIdx.x, lane = threadIdx.x;
     const int* off = a.frame_off + (size_t)s * (a.Fmax + 1);
     const int F = a.n_frames[s];
@@ -214,7 +227,36 @@ __global__ __launch_bounds__(64) void track_merged_kernel(TrackMergedArgs a) {
                 if (__any(any) && lane == 0) d_near[i] = 1;
             }
             __syncthreads();
-            for (int i = 0; i < n; ++i) {
+            for (int c = 0; HUNG && c < (a.plain ? 1 : a.ncls); ++c) {
+                int nd = 0, ng = 0;
+                if (lane == 0) {
+                    for (int i = 0; i < n; ++i)
+                        if (a.plain ? d_cl[i] >= 0 : d_cl[i] == c) g_det[nd++] = (short)i;
+                    for (int j = 0; j < nt; ++j)
+                        if (a.plain || t_cls[cur][j] == c) g_trk[ng++] = (short)j;
+                }
+                nd = __shfl(nd, 0, 64);
+                ng = __shfl(ng, 0, 64);
+                __syncthreads();
+                if (nd > 0 && ng > 0) {
+                    const bool tr = nd > ng;  // more detections than tracks: scipy solves the transpose
+                    auto cost = [&](int r, int q) {
+                        const int i = g_det[tr ? q : r], j = g_trk[tr ? r : q];
+                        const double v = pair_dist64(d_fx[i], d_fy[i], (float)t_cx[cur][j], (float)t_cy[cur][j], a.gate[d_cl[i]], d_cl[i], t_cls[cur][j]);
+                        return v > 1e18 ? 1e18 : v;
+                    };
+                    const int rows = tr ? ng : nd;
+                    (void)lsap_solve(ls, rows, tr ? nd : ng, cost);  // every cost is finite: always feasible
+                    for (int r = lane; r < rows; r += 64) {
+                        const int q = ls.col4row[r];
+                        const int i = g_det[tr ? q : r], j = g_trk[tr ? r : q];
+                        d_match[i] = cost(r, q) > 1e16 ? -2 : j;
+                        atomicOr(&taken[j >> 5], 1u << (j & 31));
+                    }
+                }
+                __syncthreads();
+            }
+            for (int i = 0; !HUNG && i < n; ++i) {
                 const int dc = d_cl[i];
                 if (dc < 0) continue;
                 const float md = a.gate[dc], dx = d_fx[i], dy = d_fy[i];
@@ -275,8 +317,10 @@ __global__ __launch_bounds__(64) void track_merged_kernel(TrackMergedArgs a) {
                     a.out_status[g0 + i] = 1; a.out_id[g0 + i] = t_id[cur][j]; a.out_ref[g0 + i] = r;
                     ++nr;
                 }
-                for (int i = 0; i < n && !err; ++i) {  // unmatched detections start tracks unless suppressed
-                    if (!TM_DIN(i) || d_match[i] >= 0) continue;
+                // unmatched detections start tracks unless suppressed (HUNG: second pass for the ones paired beyond the gate)
+                for (int pass = 0; pass < (HUNG ? 2 : 1); ++pass)
+                for (int i = 0; i < n && !err; ++i) {
+                    if (!TM_DIN(i) || d_match[i] != -1 - pass) continue;
                     if (ntrk > 0 && !(d_fl[i] & 1) && d_near[i]) continue;
                     if (nr >= TM_TCAP) { err = 2; break; }
                     const double r = (rf && !a.plain) ? be * d_sc[i] : d_sc[i];
@@ -284,7 +328,7 @@ __global__ __launch_bounds__(64) void track_merged_kernel(TrackMergedArgs a) {
                     t_cx[nxt][nr] = d_cx[i]; t_cy[nxt][nr] = d_cy[i]; t_tx[nxt][nr] = d_tx[i]; t_ty[nxt][nr] = d_ty[i];
                     t_ref[nxt][nr] = r; t_id[nxt][nr] = idc; t_age[nxt][nr] = 1; t_act[nxt][nr] = 1;
                     t_cls[nxt][nr] = d_cl[i]; t_flg[nxt][nr] = d_fl[i];
-                    a.out_status[g0 + i] = 2; a.out_id[g0 + i] = idc; a.out_ref[g0 + i] = r;
+                    a.out_status[g0 + i] = 2 + pass; a.out_id[g0 + i] = idc; a.out_ref[g0 + i] = r;
                     ++nr;
                 }
                 for (int j = 0; j < nt && !err; ++j) {  // unmatched tracks coast
@@ -330,11 +374,11 @@ extern "C" int shasta_center_greedy_f32(const float* det_xy, const float* trk_xy
     return check_launch("center_greedy");
 }
 
-extern "C" int shasta_track_merged_f64(const double* det_xy, const double* det_vel, const int32_t* det_cls, const double* det_score,
-                                       const double* det_ref, const int32_t* det_flags, const int32_t* frame_off, const double* frame_lag,
-                                       const int32_t* n_frames, int scenes, int Fmax, int n_cls, const float* cls_gate,
-                                       const int32_t* cls_ref, const double* cls_alpha, const double* cls_beta, int max_age, int plain,
-                                       int32_t* out_status, int32_t* out_id, double* out_ref, int32_t* out_err, shasta_stream_t stream) {
+static int track_merged_launch(const double* det_xy, const double* det_vel, const int32_t* det_cls, const double* det_score,
+                               const double* det_ref, const int32_t* det_flags, const int32_t* frame_off, const double* frame_lag,
+                               const int32_t* n_frames, int scenes, int Fmax, int n_cls, const float* cls_gate,
+                               const int32_t* cls_ref, const double* cls_alpha, const double* cls_beta, int max_age, int plain, int hungarian,
+                               int32_t* out_status, int32_t* out_id, double* out_ref, int32_t* out_err, shasta_stream_t stream) {
     SHASTA_REQUIRE(det_xy && det_vel && det_cls && det_score && det_ref && det_flags && frame_off && frame_lag && n_frames, "track_merged: null input");
     SHASTA_REQUIRE(cls_gate && cls_ref && cls_alpha && cls_beta && out_status && out_id && out_ref && out_err, "track_merged: null pointer");
     SHASTA_REQUIRE(scenes >= 0 && Fmax >= 1 && n_cls >= 1 && n_cls <= TM_NCLS && max_age >= 0, "track_merged: bad size (at most 8 classes)");
@@ -350,11 +394,34 @@ extern "C" int shasta_track_merged_f64(const double* det_xy, const double* det_v
         a.alpha[c] = c < n_cls ? cls_alpha[c] : 0.0;
         a.beta[c] = c < n_cls ? cls_beta[c] : 0.0;
     }
-    if (hipFuncSetAttribute((const void*)track_merged_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TM_LDS_BYTES) != hipSuccess) {
+    const void* fn = hungarian ? (const void*)track_merged_kernel<true> : (const void*)track_merged_kernel<false>;
+    const size_t lds = TM_LDS_BYTES + (hungarian ? TM_LSAP_BYTES : 0);
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
         (void)hipGetLastError();
         set_error_msg("track_merged: the device does not grant the kernel's LDS (one workgroup holds a scene's tracks): use the per-frame tracker");
         return SHASTA_E_UNSUPPORTED;
     }
-    hipLaunchKernelGGL(track_merged_kernel, dim3(scenes), dim3(64), TM_LDS_BYTES, as_stream(stream), a);
+    if (hungarian)
+        hipLaunchKernelGGL(track_merged_kernel<true>, dim3(scenes), dim3(64), lds, as_stream(stream), a);
+    else
+        hipLaunchKernelGGL(track_merged_kernel<false>, dim3(scenes), dim3(64), lds, as_stream(stream), a);
     return check_launch("track_merged");
+}
+
+extern "C" int shasta_track_merged_f64(const double* det_xy, const double* det_vel, const int32_t* det_cls, const double* det_score,
+                                       const double* det_ref, const int32_t* det_flags, const int32_t* frame_off, const double* frame_lag,
+                                       const int32_t* n_frames, int scenes, int Fmax, int n_cls, const float* cls_gate,
+                                       const int32_t* cls_ref, const double* cls_alpha, const double* cls_beta, int max_age, int plain,
+                                       int32_t* out_status, int32_t* out_id, double* out_ref, int32_t* out_err, shasta_stream_t stream) {
+    return track_merged_launch(det_xy, det_vel, det_cls, det_score, det_ref, det_flags, frame_off, frame_lag, n_frames, scenes, Fmax, n_cls, cls_gate,
+                               cls_ref, cls_alpha, cls_beta, max_age, plain, 0, out_status, out_id, out_ref, out_err, stream);
+}
+
+extern "C" int shasta_track_merged_lsap_f64(const double* det_xy, const double* det_vel, const int32_t* det_cls, const double* det_score,
+                                            const double* det_ref, const int32_t* det_flags, const int32_t* frame_off, const double* frame_lag,
+                                            const int32_t* n_frames, int scenes, int Fmax, int n_cls, const float* cls_gate,
+                                            const int32_t* cls_ref, const double* cls_alpha, const double* cls_beta, int max_age, int plain,
+                                            int32_t* out_status, int32_t* out_id, double* out_ref, int32_t* out_err, shasta_stream_t stream) {
+    return track_merged_launch(det_xy, det_vel, det_cls, det_score, det_ref, det_flags, frame_off, frame_lag, n_frames, scenes, Fmax, n_cls, cls_gate,
+                               cls_ref, cls_alpha, cls_beta, max_age, plain, 1, out_status, out_id, out_ref, out_err, stream);
 }

@@ -162,8 +162,8 @@ def _tracking_rows(results, sc, rows, merged, refine_confidence):
                  "tracking_score": ref if refine_confidence else d["detection_score"], "attribute_name": d["attribute_name"]} for d, tid, ref in items]
 
 
-def _track_scenes_on_device(predictions, scenes, max_age, merged=True, refine_confidence=False, alpha=0.5, beta=0.5):
-    """run_tracking's fast path: the greedy tracker (merged or plain) of every scene in one launch
+def _track_scenes_on_device(predictions, scenes, max_age, merged=True, refine_confidence=False, alpha=0.5, beta=0.5, hungarian=False):
+    """run_tracking's fast path: the tracker (merged or plain, greedy or Hungarian) of every scene in one launch
     (pub_tracker.track_scenes_merged_device); None when a scene exceeds the kernel's capacities or - plain tracker - a frame has
     detections but none of a tracking class (the per-frame path then raises like the reference)."""
     from .pub_tracker import track_scenes_merged_device
@@ -173,7 +173,8 @@ def _track_scenes_on_device(predictions, scenes, max_age, merged=True, refine_co
         if fr is None:
             return None
         frames.append(fr)
-    out = track_scenes_merged_device(frames, max_age=max_age, plain=not merged, refine_confidence=refine_confidence, alpha=alpha, beta=beta)
+    out = track_scenes_merged_device(frames, max_age=max_age, plain=not merged, refine_confidence=refine_confidence, alpha=alpha, beta=beta,
+                                     hungarian=hungarian)
     if any(o is None for o in out):
         return None
     annos = {"results": {}, "meta": dict(META)}
@@ -241,7 +242,7 @@ def run_tracking(predictions, frames_meta, max_age=4, hungarian=False, merged=Tr
     """pub_test.py:88-162 (merged=True, PubTrackerMerged, tracking_score = ref_detection_score) or eval.py:226-300
     (merged=False, PubTracker).  The reference walks the frames of all scenes in file order with one tracker that is reset at
     every scene start; scenes are independent, so here every scene has its own tracker and all scenes advance together, one
-    kernel launch per frame index.  whole_scenes=True (greedy assignment, either tracker): every scene's whole run is ONE kernel launch and the
+    kernel launch per frame index.  whole_scenes=True (either tracker, greedy or Hungarian): every scene's whole run is ONE kernel launch and the
     detection dicts are left untouched (the per-frame path annotates them in place, as the reference does); same rows."""
     scenes = []
     for fr in frames_meta:
@@ -249,8 +250,8 @@ def run_tracking(predictions, frames_meta, max_age=4, hungarian=False, merged=Tr
             scenes.append([])
         scenes[-1].append(fr)
     if whole_scenes:
-        if not hungarian and tracker_factory is None and _scenes_fit_device_tracker(predictions):
-            annos = _track_scenes_on_device(predictions, scenes, max_age, merged, refine_confidence, alpha, beta)
+        if tracker_factory is None and _scenes_fit_device_tracker(predictions):
+            annos = _track_scenes_on_device(predictions, scenes, max_age, merged, refine_confidence, alpha, beta, hungarian)
             if annos is not None:
                 return annos
         # beyond the kernel's capacities (or another tracker was asked for): the per-frame path below, on shallow copies - it writes

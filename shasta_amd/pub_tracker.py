@@ -5,8 +5,11 @@ Same constructor, `reset()` and `step_centertrack(results, time_lag)` contract a
 suppression rules and the confidence refinement behave identically); the distance matrix, the class / velocity gate and
 `greedy_assignment` (track_utils.py:3-14) run in one kernel launch (csrc/track.hip).  `step_batch` advances many independent
 scenes with ONE launch: the greedy loop is sequential inside a scene, so the device only pays off across scenes
-(tools/nusc_shasta/eval.py:251-259 runs the scenes one after the other).  The Hungarian option keeps scipy's solver on the
-host, fed with the device-computed matrix, like the reference."""
+(tools/nusc_shasta/eval.py:251-259 runs the scenes one after the other).  The Hungarian option (`hungarian=True`) runs on the device
+too: the float64 matrix goes from the distance kernel, clipped to 1e18 as it is read, into the batched solver of csrc/lsap.hip - scipy's
+algorithm step for step, so the same pairs - and only the assignment, the gate flags and one "cost > 1e16" bit per pair come back;
+the whole-scene kernel has the same rule (track_scenes_launch(hungarian=True)).  Only a frame with more than 1024 detections or
+tracks - beyond the solver's capacity - is still solved by scipy on the host."""
 import copy
 
 import contextlib
@@ -22,12 +25,18 @@ NUSCENES_TRACKING_NAMES = ["bicycle", "bus", "car", "motorcycle", "pedestrian", 
 NUSCENE_CLS_VELOCITY_ERROR = {"car": 2, "truck": 2, "bus": 4, "trailer": 2, "pedestrian": 0.75, "motorcycle": 2, "bicycle": 1.5}
 
 
-def center_greedy_device(problems, device=None, want_dist=True):
+LSAP_CAP = 1024  # csrc/lsap.hip: rows / columns of one problem
+
+
+def center_greedy_device(problems, device=None, want_dist=True, hungarian=False):
     """problems: list of (dets (N,2) f32, tracks (M,2) f32, det_cat (N,) i32, trk_cat (M,) i32, max_diff (N,) f32) numpy
     tuples with N, M >= 1.  Returns a list of (dist (N,M) float64 numpy or None, matched_indices (K,2) int32 numpy,
     row_any (N,) bool, col_any (M,) bool); the two flag vectors say whether a detection / a track has any partner inside
-    its gate - all the tracker needs from the matrix unless it runs the Hungarian solver, so with want_dist=False the
-    float64 matrices never leave the device."""
+    its gate - all the tracker needs from the matrix, so with want_dist=False the float64 matrices never leave the device.
+    hungarian=True: the chain continues on the stream with the batched solver over all problems (shasta_lsap_clip_f64: the clip
+    `dist[dist > 1e18] = 1e18` of pub_tracker.py:104 is applied as the solver reads); every result tuple then carries two more
+    entries: the solver's pairs (K,2) in ascending row order, K = min(N, M), and over (K,) bool = the pair's clipped cost exceeds 1e16
+    (no match, pub_tracker.py:122).  Problems of at most LSAP_CAP rows and columns."""
     lib = hip.load()
     device = device or torch.device("cuda", torch.cuda.current_device())
     S = len(problems)
@@ -51,15 +60,21 @@ def center_greedy_device(problems, device=None, want_dist=True):
     dbuf = host.to(device, non_blocking=True)
     dev = [dbuf[offs[i]:offs[i + 1]] for i in range(7)]
     dev = [dev[0].view(torch.float32), dev[1].view(torch.float32), dev[3], dev[4], dev[2].view(torch.float32), dev[5], dev[6]]
-    dist = torch.empty(S, Nmax, Mmax, dtype=torch.float64, device=device) if want_dist else None
-    out = torch.zeros(S * (2 * Nmax + Mmax), dtype=torch.int32, device=device)  # match | row_any | col_any (the flags start at zero)
-    match, row_any, col_any = out[:S * Nmax], out[S * Nmax:2 * S * Nmax], out[2 * S * Nmax:]
+    dist = torch.empty(S, Nmax, Mmax, dtype=torch.float64, device=device) if want_dist or hungarian else None
+    # match | row_any | col_any (the flags start at zero) | Hungarian: col_of_row | over | status
+    out = torch.zeros(S * (2 * Nmax + Mmax) + (S * (2 * Nmax + 1) if hungarian else 0), dtype=torch.int32, device=device)
+    match, row_any, col_any = out[:S * Nmax], out[S * Nmax:2 * S * Nmax], out[2 * S * Nmax:S * (2 * Nmax + Mmax)]
     hip.check(lib.shasta_center_greedy_f32(*[hip.ptr(x) for x in dev], S, Nmax, Mmax, hip.ptr(dist), hip.ptr(match), hip.ptr(row_any),
                                            hip.ptr(col_any), hip.stream_ptr()), "shasta_center_greedy_f32")
+    if hungarian:
+        o0 = S * (2 * Nmax + Mmax)
+        col, over, status = out[o0:o0 + S * Nmax], out[o0 + S * Nmax:o0 + 2 * S * Nmax], out[o0 + 2 * S * Nmax:]
+        hip.check(lib.shasta_lsap_clip_f64(hip.ptr(dist), hip.ptr(dev[5]), hip.ptr(dev[6]), S, Nmax, Mmax, 1e18, 1e16, hip.ptr(col), hip.ptr(over),
+                                           hip.ptr(status), hip.stream_ptr()), "shasta_lsap_clip_f64")
     out_h = out.cpu().numpy()
     match_h = out_h[:S * Nmax].reshape(S, Nmax)
     row_h = out_h[S * Nmax:2 * S * Nmax].reshape(S, Nmax) != 0
-    col_h = out_h[2 * S * Nmax:].reshape(S, Mmax) != 0
+    col_h = out_h[2 * S * Nmax:S * (2 * Nmax + Mmax)].reshape(S, Mmax) != 0
     dist_h = dist.cpu().numpy() if want_dist else None
     res = []
     for s in range(S):
@@ -67,6 +82,15 @@ def center_greedy_device(problems, device=None, want_dist=True):
         rows = np.nonzero(mi >= 0)[0]
         pairs = np.stack([rows, mi[rows]], axis=1).astype(np.int32).reshape(-1, 2)
         res.append((dist_h[s, :n[s], :m[s]].copy() if want_dist else None, pairs, row_h[s, :n[s]].copy(), col_h[s, :m[s]].copy()))
+    if hungarian:
+        lsap_h = out_h[o0:o0 + S * Nmax].reshape(S, Nmax)
+        over_h = out_h[o0 + S * Nmax:o0 + 2 * S * Nmax].reshape(S, Nmax) != 0
+        if out_h[o0 + 2 * S * Nmax:].any():  # (a distance matrix holds finite numbers only)
+            raise hip.ShastaHipError("shasta_lsap_clip_f64: status %s for a tracker problem" % sorted(set(out_h[o0 + 2 * S * Nmax:].tolist())))
+        for s in range(S):
+            ci = lsap_h[s, :n[s]]
+            rows = np.nonzero(ci >= 0)[0]
+            res[s] += (np.stack([rows, ci[rows]], axis=1).astype(np.int32).reshape(-1, 2), over_h[s, rows].copy())
     return res
 
 
@@ -107,9 +131,10 @@ class PubTracker(object):
         trk_cls = np.array([t["label_preds"] for t in self.tracks], np.int32)
         return kept, det_xy, trk_xy, det_cls, trk_cls, gate
 
-    def _finish(self, dets, det_xy, trk_xy, dist, pairs, det_near=None, trk_near=None):
+    def _finish(self, dets, det_xy, trk_xy, dist, pairs, det_near=None, trk_near=None, over=None):
         """Bookkeeping after the assignment: ids, ages, `active` counters, confidence refinement, the newborn / dead
-        suppression rules, carrying unmatched tracks for up to max_age frames."""
+        suppression rules, carrying unmatched tracks for up to max_age frames.  Hungarian: `over` (one bool per pair: cost > 1e16)
+        stands for the matrix; without it the bits are taken from `dist`."""
         n_det, n_trk = det_xy.shape[0], trk_xy.shape[0]
         taken_d, taken_t = set(pairs[:, 0].tolist()), set(pairs[:, 1].tolist())
         free_dets = [i for i in range(n_det) if i not in taken_d]
@@ -120,9 +145,10 @@ class PubTracker(object):
             trk_near = np.array([(dist[:, j] <= self.NUSCENE_CLS_VELOCITY_ERROR[self.tracks[j]["detection_name"]]).sum() > 0
                                  for j in range(n_trk)], bool)
         if self.hungarian:  # the solver pairs everything: pairs at the invalid cost are not matches
-            good = [p for p in pairs if not dist[p[0], p[1]] > 1e16]
-            free_dets += [p[0] for p in pairs if dist[p[0], p[1]] > 1e16]
-            pairs = np.array(good).reshape(-1, 2)
+            if over is None:
+                over = [dist[p[0], p[1]] > 1e16 for p in pairs]
+            free_dets += [p[0] for p, o in zip(pairs, over) if o]
+            pairs = np.array([p for p, o in zip(pairs, over) if not o]).reshape(-1, 2)
         out = []
         for i, j in pairs:
             det, old = dets[i], self.tracks[j]
@@ -155,6 +181,7 @@ class PubTracker(object):
         return out
 
     def _host_assign(self, dist):
+        """scipy on the host: only for a problem beyond the device solver's capacity (_solve)."""
         from scipy.optimize import linear_sum_assignment
         d = dist.copy()
         d[d > 1e18] = 1e18
@@ -174,8 +201,7 @@ def step_batch(trackers, results_list, time_lags):
         if p is not None and len(p[2]) > 0:  # not the first frame of the scene
             where.append(k)
             problems.append((p[1], p[2], p[3], p[4], p[5]))
-    need_dist = any(trackers[k].hungarian for k in where)  # only the Hungarian solver needs the matrices on the host
-    solved = dict(zip(where, center_greedy_device(problems, want_dist=need_dist))) if problems else {}
+    solved = dict(zip(where, _solve(problems, any(trackers[k].hungarian for k in where)))) if problems else {}
     outs = []
     for k, trk in enumerate(trackers):
         p = prepared[k]
@@ -184,16 +210,33 @@ def step_batch(trackers, results_list, time_lags):
             outs.append([])
             continue
         results, dets, tracks = p[0], p[1], p[2]
-        det_near = trk_near = None
+        det_near = trk_near = over = None
         if k in solved:
-            dist, matched, det_near, trk_near = solved[k]
-            if trk.hungarian:
-                dist, matched = trk._host_assign(dist)
+            dist, matched, det_near, trk_near, over = _assignment(trk, solved[k])
         else:
             assert len(trk.tracks) == 0
             dist, matched = None, np.array([], np.int32).reshape(-1, 2)
-        outs.append(trk._finish(results, dets, tracks, dist, matched, det_near, trk_near))
+        outs.append(trk._finish(results, dets, tracks, dist, matched, det_near, trk_near, over))
     return outs
+
+
+def _solve(problems, hungarian):
+    """The device step of one frame index.  Hungarian trackers: distance kernel, clip and solver in one chain, no matrix comes back -
+    unless a problem exceeds the solver's capacity: then, as before, the matrices come back and scipy solves on the host."""
+    if hungarian and max(max(p[0].shape[0], p[1].shape[0]) for p in problems) > LSAP_CAP:
+        return center_greedy_device(problems, want_dist=True)
+    return center_greedy_device(problems, want_dist=False, hungarian=hungarian)
+
+
+def _assignment(trk, solved):
+    """(dist, pairs, det_near, trk_near, over) of one problem for this tracker's rule from what _solve returned for it."""
+    dist, matched, det_near, trk_near = solved[:4]
+    if not trk.hungarian:
+        return dist, matched, det_near, trk_near, None
+    if len(solved) == 6:
+        return None, solved[4], det_near, trk_near, solved[5]
+    dist, matched = trk._host_assign(dist)
+    return dist, matched, det_near, trk_near, None
 
 
 # per-class confidence-refinement parameters of the merged tracker (pub_tracker_merged.py:34-42)
@@ -258,7 +301,7 @@ class PubTrackerMerged(object):
             per_class.append((name, dets, tracks, det_xy, trk_xy, det_cls, trk_cls, gate))
         return per_class
 
-    def _finish_class(self, name, dets, tracks, dist, pairs, det_near, trk_near, ret):
+    def _finish_class(self, name, dets, tracks, dist, pairs, det_near, trk_near, ret, over=None):
         n_det, n_trk = len(dets), len(tracks)
         taken_d, taken_t = set(pairs[:, 0].tolist()), set(pairs[:, 1].tolist())
         free_dets = [i for i in range(n_det) if i not in taken_d]
@@ -268,9 +311,10 @@ class PubTrackerMerged(object):
             det_near = np.array([(dist[i, :] <= gate).sum() > 0 for i in range(n_det)], bool)
             trk_near = np.array([(dist[:, j] <= gate).sum() > 0 for j in range(n_trk)], bool)
         if self.hungarian:
-            good = [p for p in pairs if not dist[p[0], p[1]] > 1e16]
-            free_dets += [p[0] for p in pairs if dist[p[0], p[1]] > 1e16]
-            pairs = np.array(good).reshape(-1, 2)
+            if over is None:
+                over = [dist[p[0], p[1]] > 1e16 for p in pairs]
+            free_dets += [p[0] for p, o in zip(pairs, over) if o]
+            pairs = np.array([p for p, o in zip(pairs, over) if not o]).reshape(-1, 2)
         ref = self.trk_ref[name]
         for i, j in pairs:
             det, old = dets[i], tracks[j]
@@ -326,8 +370,7 @@ def step_batch_merged(trackers, results_list, time_lags):
             if len(p[4]) > 0:
                 where.append((k, c))
                 problems.append((p[3], p[4], p[5], p[6], p[7]))
-    need_dist = any(trackers[k].hungarian for k, _ in where)
-    solved = dict(zip(where, center_greedy_device(problems, want_dist=need_dist))) if problems else {}
+    solved = dict(zip(where, _solve(problems, any(trackers[k].hungarian for k, _ in where)))) if problems else {}
     outs = []
     for k, trk in enumerate(trackers):
         per_class = prepared[k]
@@ -337,30 +380,29 @@ def step_batch_merged(trackers, results_list, time_lags):
             continue
         ret = []
         for c, (name, dets, tracks, det_xy, trk_xy, _, _, _) in enumerate(per_class):
-            det_near = trk_near = None
+            det_near = trk_near = over = None
             if (k, c) in solved:
-                dist, matched, det_near, trk_near = solved[(k, c)]
-                if trk.hungarian:
-                    dist, matched = trk._host_assign(dist)
+                dist, matched, det_near, trk_near, over = _assignment(trk, solved[(k, c)])
             else:
                 assert len(tracks) == 0
                 dist, matched = None, np.array([], np.int32).reshape(-1, 2)
-            trk._finish_class(name, dets, tracks, dist, matched, det_near, trk_near, ret)
+            trk._finish_class(name, dets, tracks, dist, matched, det_near, trk_near, ret, over)
         trk.tracks = ret
         outs.append(ret)
     return outs
 
 
-def track_scenes_merged_device(scene_frames, max_age=0, device=None, plain=False, refine_confidence=False, alpha=0.5, beta=0.5):
+def track_scenes_merged_device(scene_frames, max_age=0, device=None, plain=False, refine_confidence=False, alpha=0.5, beta=0.5, hungarian=False):
     """track_scenes_collect(track_scenes_launch(...)): see there."""
     return track_scenes_collect(track_scenes_launch(scene_frames, max_age=max_age, device=device, plain=plain, refine_confidence=refine_confidence,
-                                                    alpha=alpha, beta=beta))
+                                                    alpha=alpha, beta=beta, hungarian=hungarian))
 
 
-def track_scenes_launch(scene_frames, max_age=0, device=None, plain=False, refine_confidence=False, alpha=0.5, beta=0.5, stream=None):
-    """The merged tracker (PubTrackerMerged, greedy; plain=True: PubTracker with its refine_confidence / alpha / beta - one list over all
+def track_scenes_launch(scene_frames, max_age=0, device=None, plain=False, refine_confidence=False, alpha=0.5, beta=0.5, stream=None, hungarian=False):
+    """The merged tracker (PubTrackerMerged; plain=True: PubTracker with its refine_confidence / alpha / beta - one list over all
     tracking classes, result order matched detections then new ones) for whole scenes in ONE launch (csrc/track.hip `track_merged_kernel`,
-    shasta_track_merged_f64): scene_frames = [[(detections of the frame: list of nuScenes-format dicts with `ref_detection_score`,
+    shasta_track_merged_f64, greedy; hungarian=True: shasta_track_merged_lsap_f64, the trackers' `hungarian=True` - new rows then come
+    never-paired detections first, the ones the solver paired beyond the gate after them): scene_frames = [[(detections of the frame: list of nuScenes-format dicts with `ref_detection_score`,
     time_lag), ...] per scene].  Returns per scene, per frame, the result rows' sources in the order pub_test.py emits them:
     a list of (detection dict, tracking_id, refined ref_detection_score) - class by class, matched detections then new ones - or None
     when a scene exceeds the kernel's capacities (512 detections per frame, 768 tracks alive): the caller then takes the per-frame path.
@@ -428,13 +470,14 @@ def track_scenes_launch(scene_frames, max_age=0, device=None, plain=False, refin
             refon = (C.c_int32 * len(names))(*[int(bool(TRK_REF[n]["ref"])) for n in names])
             alpha = (C.c_double * len(names))(*[float(TRK_REF[n]["alpha"]) for n in names])
             beta = (C.c_double * len(names))(*[float(TRK_REF[n]["beta"]) for n in names])
-        rc = lib.shasta_track_merged_f64(hip.ptr(seg[0]), hip.ptr(seg[1]), hip.ptr(seg[4].view(torch.int32)), hip.ptr(seg[2]), hip.ptr(seg[3]),
-                                         hip.ptr(seg[5].view(torch.int32)), hip.ptr(seg[6].view(torch.int32)), hip.ptr(seg[7]),
-                                         hip.ptr(seg[8].view(torch.int32)), S, Fmax, len(names), gate, refon, alpha, beta, int(max_age), int(bool(plain)),
-                                         hip.ptr(o_st), hip.ptr(o_id), hip.ptr(o_ref), hip.ptr(o_err), hip.stream_ptr())
+        launch = lib.shasta_track_merged_lsap_f64 if hungarian else lib.shasta_track_merged_f64
+        rc = launch(hip.ptr(seg[0]), hip.ptr(seg[1]), hip.ptr(seg[4].view(torch.int32)), hip.ptr(seg[2]), hip.ptr(seg[3]),
+                    hip.ptr(seg[5].view(torch.int32)), hip.ptr(seg[6].view(torch.int32)), hip.ptr(seg[7]),
+                    hip.ptr(seg[8].view(torch.int32)), S, Fmax, len(names), gate, refon, alpha, beta, int(max_age), int(bool(plain)),
+                    hip.ptr(o_st), hip.ptr(o_id), hip.ptr(o_ref), hip.ptr(o_err), hip.stream_ptr())
         if rc == hip.E_UNSUPPORTED:  # a device that does not grant the kernel its LDS: every scene takes the per-frame path
             return dict(done=[None] * S)
-        hip.check(rc, "shasta_track_merged_f64")
+        hip.check(rc, "shasta_track_merged_lsap_f64" if hungarian else "shasta_track_merged_f64")
         back = torch.empty(out.shape, dtype=out.dtype, pin_memory=device.type == "cuda")
         back.copy_(out, non_blocking=True)
         ev = None
@@ -457,7 +500,8 @@ def track_scenes_collect(handle):
     r_st = oh[D:D + (D + 1) // 2].view(np.int32)[:D]
     r_id = oh[D + (D + 1) // 2:D + 2 * ((D + 1) // 2)].view(np.int32)[:D].tolist()
     r_err = oh[D + 2 * ((D + 1) // 2):].view(np.int32)[:S]
-    # result order inside a frame: class, then matched before new, then file order - one sort for the whole split
+    # result order inside a frame: class, then matched (status 1) before new (2) before - Hungarian - new ones that the solver had paired
+    # beyond the gate (3), then file order - one sort for the whole split
     frame_of = np.zeros(D, np.int64)
     bounds, fid = [], 0
     for s in range(S):

@@ -1,7 +1,8 @@
 import atexit
 import shutil
 """GPU-box helper: where the merged tracker's time goes on the 20 x 40 synthetic split (after one chain run has produced `merged`).
-    python tools/profile_tracker.py"""
+    python tools/profile_tracker.py
+    python tools/profile_tracker.py --hungarian    # hungarian=True: host solver per frame / device solver per frame / whole scenes"""
 import cProfile
 import gc
 import os
@@ -40,14 +41,26 @@ def main():
     pub_tracker.PubTrackerMerged._prepare = timed("prepare", orig_prepare)
     pub_tracker.center_greedy_device = timed("device", orig_dev)
     pub_tracker.PubTrackerMerged._finish_class = timed("finish", orig_fin)
-    for rep in range(3):
-        for k in acc:
-            acc[k] = 0.0
-        preds = {tok: [dict(d) for d in annos] for tok, annos in merged["results"].items()}
-        t0 = time.perf_counter()
-        pipeline.run_tracking(preds, meta, max_age=4)
-        total = time.perf_counter() - t0
-        print("tracker %.3f s: " % total + ", ".join("%s %.3f" % kv for kv in acc.items()) + ", rest %.3f" % (total - sum(acc.values())), flush=True)
+    # --hungarian: the three routes of hungarian=True.  LSAP_CAP = 0 sends every problem down the over-capacity route, which is the
+    # route every problem took before the device solver: float64 matrices back to the host, scipy per problem
+    cap = pub_tracker.LSAP_CAP
+    modes = [("tracker", {}, cap)]
+    if "--hungarian" in sys.argv:
+        modes = [("hungarian, per frame, scipy on the host", dict(hungarian=True), 0), ("hungarian, per frame, device solver", dict(hungarian=True), cap),
+                 ("hungarian, whole scenes in one launch", dict(hungarian=True, whole_scenes=True), cap)]
+    want = None
+    for rep in range(5 if len(modes) > 1 else 3):  # the routes take turns: a difference has to show in every round (the first is warm-up)
+        for name, kw, lsap_cap in modes:
+            pub_tracker.LSAP_CAP = lsap_cap
+            for k in acc:
+                acc[k] = 0.0
+            preds = {tok: [dict(d) for d in annos] for tok, annos in merged["results"].items()}
+            t0 = time.perf_counter()
+            got = pipeline.run_tracking(preds, meta, max_age=4, **kw)
+            total = time.perf_counter() - t0
+            print("%s %.3f s: " % (name, total) + ", ".join("%s %.3f" % kv for kv in acc.items()) + ", rest %.3f" % (total - sum(acc.values())), flush=True)
+            want = want or got
+            assert got == want, "the routes disagree"
 
 
 if __name__ == "__main__":
