@@ -554,6 +554,36 @@ int shasta_lsap_clip_f64(const double* cost, const int32_t* n, const int32_t* m,
                          double over_above, int32_t* col_of_row, int32_t* over, int32_t* status, shasta_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Ground-truth affinity labels: replaces preprocessing/make_gt_shasta.py:81-152 over preprocessing/gt_association/associate.py:6-80
+ * (`distance_type="l2"`) for all frames of all scenes of a split in ONE call (two kernels on `stream`, no workspace).
+ * Frame f holds detections det_off[f] .. det_off[f+1]-1 and ground-truth boxes gt_off[f] .. gt_off[f+1]-1 of the flat arrays
+ * ((frames+1,) int32 offsets, device); the frames of a scene are consecutive and in order, the previous frame of f is f-1.
+ *  det_xy (total_det,2) / gt_xy (total_gt,2) float64 centres, det_score (total_det,) float64
+ *  det_type (total_det,) int32 index into type_mask; gt_type (total_gt,) int32 in 0..63
+ *  type_mask (n_det_types,) uint64, 8-byte aligned: bit t of entry d = a detection of type d may take a ground-truth box of type t
+ *  (the caller evaluates the reference's `pred_type in gt_type` once per pair of distinct values)
+ *  gt_id (total_gt,) int32 instance ids, unique within a frame; has_prev / emit (frames,) int32 flags
+ * Association per frame (one wavefront): detections in descending score order, of equal scores the larger index first; each takes
+ * the nearest ground-truth box not yet taken whose type is compatible, dist = sqrt(dx*dx + dy*dy) in float64 (every operation
+ * rounded, as np.linalg.norm), the lowest index among equal distances, if dist < threshold (strict).
+ *  gt_of_det (total_det,) int32: the ground-truth box (index within the frame) of every detection, -1 = false positive
+ * Link per frame with emit != 0:
+ *  newborn (total_det,) int32 0/1 at the frame's detections: matched, and - with has_prev - no matched detection of frame f-1
+ *  holds the same id
+ *  col_of_prev (total_det,) int32 at the detections of frame f-1 (has_prev != 0 only), K = detections of frame f: 0..K-1 = the
+ *  detection of f whose box has the same id, K = dead track, K+1 = false negative (the id is in frame f, no detection took it) -
+ *  the one-hot column of the reference's `matched` row
+ * Entries of newborn / col_of_prev outside these are not written.  A frame whose offsets leave [0, total] or whose counts exceed
+ * max_det / max_gt is skipped.  max_det <= 1024, max_gt <= 512 (a frame's state lives in LDS), beyond: SHASTA_E_UNSUPPORTED before
+ * any launch.
+ * ------------------------------------------------------------------------------------------ */
+int shasta_gt_labels_f64(const double* det_xy, const double* det_score, const int32_t* det_type, const int32_t* det_off,
+                         const double* gt_xy, const int32_t* gt_type, const int32_t* gt_id, const int32_t* gt_off,
+                         const uint64_t* type_mask, int n_det_types, const int32_t* has_prev, const int32_t* emit, int frames,
+                         int total_det, int total_gt, int max_det, int max_gt, double threshold, int32_t* gt_of_det,
+                         int32_t* col_of_prev, int32_t* newborn, shasta_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Training path, backward helpers (the nn.Linear layers run on shasta_gemm_strided_f32; the first layer of each pair MLP
  * is factorised over the table rows).  Replaces what torch autograd derives from det3d/models/tracker/shasta.py:241-325 in
  * tools/nusc_shasta/train.py:198-213.

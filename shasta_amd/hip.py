@@ -136,6 +136,7 @@ SYMBOLS = {
     "shasta_track_merged_lsap_f64": (_I, [_P] * 9 + [_I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "shasta_lsap_f64": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "shasta_lsap_clip_f64": (_I, [_P, _P, _P, _I, _I, _I, C.c_double, C.c_double, _P, _P, _P, _P]),
+    "shasta_gt_labels_f64": (_I, [_P] * 9 + [_I, _P, _P, _I, _I, _I, _I, _I, C.c_double, _P, _P, _P, _P]),
     "shasta_decode_flags_f32": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "shasta_gemm_strided_f32": (_I, [_P, C.c_long, C.c_long, _P, C.c_long, C.c_long, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _Z, _P]),
     "shasta_gemm_strided_group_f32": (_I, [_I, _P, _P, _P, _P, _P, C.c_long, C.c_long, C.c_long, C.c_long, _I, _I, _I, _I, _I, _I, _P, _Z, _P]),
