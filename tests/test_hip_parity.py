@@ -322,12 +322,19 @@ def _conv_models(n, cin, seed0=20):
 
 
 @pytest.mark.parametrize("heads,B,cin,H,W", [(7, 1, 64, 40, 180), (3, 2, 24, 9, 37), (8, 1, 16, 5, 7), (2, 1, 512, 180, 180),
-                                             (7, 3, 32, 90, 180), (4, 2, 512, 180, 180), (8, 5, 16, 61, 183), (6, 24, 16, 23, 30)])
+                                             (7, 3, 32, 90, 180), (4, 2, 512, 180, 180), (8, 5, 16, 61, 183), (6, 24, 16, 23, 30),
+                                             (2, 16, 16, 20, 180), (2, 16, 48, 20, 180), (2, 64, 16, 3, 183), (3, 43, 16, 3, 183)])
 def test_shared_conv_bank_equals_the_single_heads_and_the_oracle(heads, B, cin, H, W):
     """shasta_shared_conv_multi_f32: the class heads of tools/nusc_shasta/eval.py:86-101 in one launch.  Every head's output is
     bit-identical to that model's own shared_conv_nhwc (heads = 1) and within the K0 tolerance of the oracle; the packed images follow a
-    change of a head's tensors.  The last four cases are large enough (>= 512 tiles x maps x heads) for the 512-pixel-tile kernel
-    (shared_conv_f16w_kernel) while the single-head calls take the 256-pixel one: the two forms give the same bits."""
+    change of a head's tensors.  Which form of the kernel a call takes (the launcher's rule, with tiles = ceil(H W / 512) and maps =
+    2 B here): tiles x maps x heads >= 512 and three heads or more: the input cut once for all heads (shared_conv_f16p_kernel) - cases
+    5 to 8 and the last one; the same product with fewer heads: 512-pixel tiles (shared_conv_f16w_kernel) - cases 9 to 11; everything
+    else, every single-head call of this test included: 256-pixel tiles (shared_conv_f16_kernel).  So the bit equality below compares the
+    two larger forms with the 256-pixel one.  Cases 9 and 10 have one and three chunks of 16 channels (the prologue that stages the only
+    chunk twice; the odd tail of the two-trips-per-iteration loop).  Cases 11 and 12 are the widest map the fp16 kernel serves (183
+    columns: shasta_shared_conv_f16x2_supported) in either larger form: 549 pixels, so the second tile starts in the middle of a row
+    (pixel 512 = row 2, column 146) and holds 37 pixels."""
     from shasta_amd.shared_conv import SharedConvBank
     dev = _dev()
     ms = _conv_models(heads, cin)
@@ -360,7 +367,9 @@ def test_shared_conv_with_a_caller_supplied_bound(heads, B, cin, H, W):
     """shasta_shared_conv_multi_bounded_f32: the producer of the maps names their largest magnitude and the pass that finds it is skipped.
     A bound in the true maximum's binade gives the same bits; a loose one (6 x) too, up to elements whose low piece goes subnormal (a
     power-of-two scale commutes with fp16's rounding; a piece pair keeps 22 bits of every element within 2^-17 of the bound); an input far
-    beyond the bound comes out non-finite, never as a wrong finite number.  All three forms of the kernel (256-pixel tiles, 512-pixel tiles, the input cut once for all heads)."""
+    beyond the bound comes out non-finite, never as a wrong finite number.  The first two cases take the 256-pixel tiles (8 tiles x 16 maps x
+    3 heads = 384 stays below the 512 the larger forms start at), the last one the input cut once for all heads; the bound only replaces
+    the maxima pass in front of the kernels, the 512-pixel form is covered by test_shared_conv_bank_equals_the_single_heads_and_the_oracle."""
     from shasta_amd.shared_conv import SharedConvBank
     dev = _dev()
     ms = _conv_models(heads, cin, seed0=40)
