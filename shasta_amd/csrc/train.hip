@@ -402,8 +402,10 @@ __global__ void abs_kernel(const float* __restrict__ x, const float* __restrict_
 // no amsgrad), one pass over p, g, m, v instead of the seven multi-tensor passes of the unfused optimizer:
 //   g' = g + wd*p ; m += (g' - m)*(1-b1) ; v = b2*v + (1-b2)*g'*g' ; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
 struct AdamArgs {
-    float lr_over_bc1, beta1, beta2, eps, weight_decay, rsqrt_bc2;
-    // non-null: everything that changes from step to step comes from DEVICE memory (dyn = {lr / bc1, 1 / sqrt(bc2), beta1, beta2},
+    // one_minus_beta: 1 - beta formed in DOUBLE from the caller's double beta and rounded once, like torch's scalars.  1.0f - (float)beta
+    // carries beta's own rounding error relative to the thousand times smaller 1 - beta (0.999f: 1.3e-5 of every g*g added to v)
+    float lr_over_bc1, beta1, beta2, one_minus_beta1, one_minus_beta2, eps, weight_decay, rsqrt_bc2;
+    // non-null: everything that changes from step to step comes from DEVICE memory (dyn = {lr / bc1, 1 / sqrt(bc2), beta1, beta2, 1 - beta1, 1 - beta2},
     // written by adam_prepare_kernel from a device-side step counter and the scheduler's lr / betas) - a training step replayed from a
     // captured hipGraph cannot take them as launch arguments, which are frozen at capture time
     const float* dyn;
@@ -414,26 +416,31 @@ __device__ __forceinline__ AdamArgs adam_resolve(AdamArgs a) {
         a.rsqrt_bc2 = a.dyn[1];
         a.beta1 = a.dyn[2];
         a.beta2 = a.dyn[3];
+        a.one_minus_beta1 = a.dyn[4];
+        a.one_minus_beta2 = a.dyn[5];
     }
     return a;
 }
-// one step of the device-side schedule: ++*step; hyper = {lr, beta1, beta2} -> dyn = {lr / (1 - beta1^step), 1 / sqrt(1 - beta2^step), beta1, beta2}
-__global__ void adam_prepare_kernel(int* __restrict__ step, const float* __restrict__ hyper, float* __restrict__ dyn) {
+// one step of the device-side schedule: ++*step; hyper = {lr, beta1, beta2} (doubles, the host's own values) ->
+// dyn = {lr / (1 - beta1^step), 1 / sqrt(1 - beta2^step), beta1, beta2, 1 - beta1, 1 - beta2}: what make_adam_args computes on the host
+__global__ void adam_prepare_kernel(int* __restrict__ step, const double* __restrict__ hyper, float* __restrict__ dyn) {
     if (threadIdx.x || blockIdx.x) return;
     const int s = *step + 1;
     *step = s;
-    const float beta1 = hyper[1], beta2 = hyper[2];
-    const double bc1 = 1.0 - pow((double)beta1, (double)s), bc2 = 1.0 - pow((double)beta2, (double)s);
-    dyn[0] = (float)((double)hyper[0] / bc1);
+    const double beta1 = hyper[1], beta2 = hyper[2];
+    const double bc1 = 1.0 - pow(beta1, (double)s), bc2 = 1.0 - pow(beta2, (double)s);
+    dyn[0] = (float)(hyper[0] / bc1);
     dyn[1] = (float)(1.0 / sqrt(bc2));
-    dyn[2] = beta1;
-    dyn[3] = beta2;
+    dyn[2] = (float)beta1;
+    dyn[3] = (float)beta2;
+    dyn[4] = (float)(1.0 - beta1);
+    dyn[5] = (float)(1.0 - beta2);
 }
 
 __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, const AdamArgs& a) {
     g = fmaf(a.weight_decay, p, g);
-    m = fmaf(g - m, 1.0f - a.beta1, m);
-    v = fmaf(1.0f - a.beta2, g * g, a.beta2 * v);
+    m = fmaf(g - m, a.one_minus_beta1, m);
+    v = fmaf(a.one_minus_beta2, g * g, a.beta2 * v);
     const float denom = fmaf(sqrtf(v), a.rsqrt_bc2, a.eps);
     p = p - a.lr_over_bc1 * (m / denom);
 }
@@ -983,15 +990,17 @@ extern "C" int shasta_bev_gather_bwd_f32(const float* dfeat, int B, int H, int W
     return check_launch("bev_gather_bwd");
 }
 
-// d_dyn (device, 4 floats, or NULL): when given, lr, betas and step are ignored - the kernels read lr / bc1, 1 / sqrt(bc2) and the betas
+// d_dyn (device, 6 floats, or NULL): when given, lr, betas and step are ignored - the kernels read lr / bc1, 1 / sqrt(bc2) and the betas
 // from it (shasta_adam_prepare_f32 writes them from a device-side step counter and {lr, beta1, beta2} once per optimizer step)
-static AdamArgs make_adam_args(float lr, float beta1, float beta2, float eps, float weight_decay, int step, const float* d_dyn) {
+static AdamArgs make_adam_args(double lr, double beta1, double beta2, float eps, float weight_decay, int step, const float* d_dyn) {
     const double s = step >= 1 ? (double)step : 1.0;
-    const double bc1 = 1.0 - pow((double)beta1, s), bc2 = 1.0 - pow((double)beta2, s);
+    const double bc1 = 1.0 - pow(beta1, s), bc2 = 1.0 - pow(beta2, s);
     AdamArgs a;
-    a.lr_over_bc1 = (float)((double)lr / bc1);
-    a.beta1 = beta1;
-    a.beta2 = beta2;
+    a.lr_over_bc1 = (float)(lr / bc1);
+    a.beta1 = (float)beta1;
+    a.beta2 = (float)beta2;
+    a.one_minus_beta1 = (float)(1.0 - beta1);
+    a.one_minus_beta2 = (float)(1.0 - beta2);
     a.eps = eps;
     a.weight_decay = weight_decay;
     a.rsqrt_bc2 = (float)(1.0 / sqrt(bc2));
@@ -999,14 +1008,14 @@ static AdamArgs make_adam_args(float lr, float beta1, float beta2, float eps, fl
     return a;
 }
 
-extern "C" int shasta_adam_prepare_f32(int* d_step, const float* d_hyper, float* d_dyn, shasta_stream_t stream) {
+extern "C" int shasta_adam_prepare_f32(int* d_step, const double* d_hyper, float* d_dyn, shasta_stream_t stream) {
     SHASTA_REQUIRE(d_step && d_hyper && d_dyn, "adam_prepare: null pointer");
     hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(1), 0, as_stream(stream), d_step, d_hyper, d_dyn);
     return check_launch("adam_prepare");
 }
 
-extern "C" int shasta_adam_step_f32(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, float lr, float beta1,
-                                    float beta2, float eps, float weight_decay, int step, const float* d_dyn, shasta_stream_t stream) {
+extern "C" int shasta_adam_step_f32(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, double lr, double beta1,
+                                    double beta2, float eps, float weight_decay, int step, const float* d_dyn, shasta_stream_t stream) {
     SHASTA_REQUIRE(param && grad && exp_avg && exp_avg_sq && n >= 0 && (step >= 1 || d_dyn), "adam_step: bad argument");
     SHASTA_REQUIRE((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0,
                    "adam_step: tensors must be 16-byte aligned");
@@ -1018,7 +1027,7 @@ extern "C" int shasta_adam_step_f32(float* param, const float* grad, float* exp_
 }
 
 extern "C" int shasta_adam_multi_f32(int count, float* const* param, const float* const* grad, float* const* exp_avg,
-                                     float* const* exp_avg_sq, const long* n, float lr, float beta1, float beta2, float eps,
+                                     float* const* exp_avg_sq, const long* n, double lr, double beta1, double beta2, float eps,
                                      float weight_decay, int step, const float* d_dyn, shasta_stream_t stream) {
     SHASTA_REQUIRE(count >= 0 && (step >= 1 || d_dyn) && (count == 0 || (param && grad && exp_avg && exp_avg_sq && n)), "adam_multi: bad argument");
     const AdamArgs a = make_adam_args(lr, beta1, beta2, eps, weight_decay, step, d_dyn);
@@ -1057,7 +1066,7 @@ extern "C" size_t shasta_adam_lowrank_dx_workspace_bytes(int H, int K, int Rdx) 
 
 extern "C" int shasta_adam_lowrank_dx_f32(float* param, float* exp_avg, float* exp_avg_sq, int H, int K, const float* G, int ldg, const float* X,
                                           int ldx, int R, const float* Gdx, int ldgdx, int Rdx, float* Y, long ldy, int accumulate, void* workspace,
-                                          size_t workspace_bytes, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                                          size_t workspace_bytes, double lr, double beta1, double beta2, float eps, float weight_decay, int step,
                                           const float* d_dyn, shasta_stream_t stream) {
     SHASTA_REQUIRE(param && exp_avg && exp_avg_sq && G && X && Gdx && Y && workspace && H >= 1 && K >= 4 && (step >= 1 || d_dyn), "adam_lowrank_dx: bad argument");
     SHASTA_REQUIRE(R >= 1 && R <= 64 && Rdx >= 1 && Rdx <= 16, "adam_lowrank_dx: 1 <= R <= 64, 1 <= Rdx <= 16");
@@ -1088,7 +1097,7 @@ extern "C" int shasta_adam_lowrank_dx_f32(float* param, float* exp_avg, float* e
 }
 
 extern "C" int shasta_adam_lowrank_f32(float* param, float* exp_avg, float* exp_avg_sq, int H, int K, const float* G, int ldg, const float* X,
-                                       int ldx, int R, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                                       int ldx, int R, double lr, double beta1, double beta2, float eps, float weight_decay, int step,
                                        const float* d_dyn, shasta_stream_t stream) {
     SHASTA_REQUIRE(param && exp_avg && exp_avg_sq && G && X && H >= 0 && K >= 0 && (step >= 1 || d_dyn), "adam_lowrank: bad argument");
     SHASTA_REQUIRE(R >= 1 && R <= 64, "adam_lowrank: 1 <= R <= 64 (frame-pairs of a step over all ranks)");

@@ -613,7 +613,10 @@ class FusedAdam(torch.optim.Optimizer):
         # sync_hyper() copies them over (called by step() itself outside a capture, by GraphedTrainStep before every replay).  One
         # step counter per parameter group (every tensor of a group is stepped together, as in the reference's loop).
         self.capturable = bool(capturable)
-        self._armed = {}  # id(group) -> the group's factors are prepared for the current optimizer step
+        # group index -> the group's device-side step counter, its schedule values and the host's copy of both.  Kept HERE and not in
+        # param_groups: state_dict() is a checkpoint (numbers only), and load_state_dict() replaces the group dicts while a captured
+        # graph keeps the addresses of these buffers.
+        self._dev_state = {}
         if lowrank_first_layers is not None:
             lowrank_first_layers.lowrank_adam = True
             import weakref
@@ -627,47 +630,123 @@ class FusedAdam(torch.optim.Optimizer):
             st["exp_avg_sq"] = torch.zeros_like(p)
         return st
 
-    def _dev(self, group, device):
-        d = group.get("_shasta_dev")
+    def _group_step(self, group):
+        """The step number a group's counter stands at: the largest state['step'] of its parameters (0 before the first step)."""
+        return max([int(self.state[p]["step"]) for p in group["params"] if self.state.get(p)], default=0)
+
+    def _seed(self, d, count):
+        """Set a group's counter, on the device (in place: a captured graph holds its address) and in the host's mirror."""
+        d["step"].fill_(int(count))
+        d["count"], d["armed"], d["host"] = int(count), False, None
+
+    def _dev(self, gi, device):
+        d = self._dev_state.get(gi)
         if d is None or d["step"].device != device:
-            d = group["_shasta_dev"] = dict(step=torch.zeros(1, dtype=torch.int32, device=device), hyper=torch.zeros(3, device=device),
-                                            dyn=torch.zeros(4, device=device), host=None)
+            d = self._dev_state[gi] = dict(step=torch.zeros(1, dtype=torch.int32, device=device), hyper=torch.zeros(3, dtype=torch.float64, device=device),
+                                           dyn=torch.zeros(6, device=device), host=None, count=0, armed=False)
+            self._seed(d, self._group_step(self.param_groups[gi]))  # a loaded checkpoint's step, not 0: bias correction goes on from there
         return d
+
+    def device_step(self, group_index=0):
+        """capturable: the group's step counter as it stands in device memory (synchronises; None before the group's first step)."""
+        d = self._dev_state.get(group_index)
+        return None if d is None else int(d["step"])
 
     def sync_hyper(self):
         """capturable: copy every group's lr / betas (the scheduler's host values) to the device; a no-op when nothing changed."""
-        for group in self.param_groups:
-            d = group.get("_shasta_dev")
-            if d is None:
-                continue
+        for gi, d in self._dev_state.items():
+            group = self.param_groups[gi]
             host = (float(group["lr"]), float(group["betas"][0]), float(group["betas"][1]))
             if d["host"] != host:
-                d["hyper"].copy_(torch.tensor(host, dtype=torch.float32), non_blocking=False)
+                d["hyper"].copy_(torch.tensor(host, dtype=torch.float64), non_blocking=False)
                 d["host"] = host
 
-    def _dyn(self, group, device):
+    def _dyn(self, gi, device):
         """Device pointer of the group's step factors for the CURRENT optimizer step (None in the plain mode).  The first use in a step -
         inside the backward when the first layers step there, else in step() - advances the device-side counter."""
         if not self.capturable:
             return None
-        d = self._dev(group, device)
-        if not self._armed.get(id(group)):
+        d = self._dev(gi, device)
+        if not d["armed"]:
             if d["host"] is None or not torch.cuda.is_current_stream_capturing():
                 if torch.cuda.is_current_stream_capturing() and d["host"] is None:
                     raise hip.ShastaHipError("FusedAdam(capturable=True): run one eager step (or sync_hyper()) before capturing")
                 self.sync_hyper()
             hip.check(hip.load().shasta_adam_prepare_f32(hip.ptr(d["step"]), hip.ptr(d["hyper"]), hip.ptr(d["dyn"]), hip.stream_ptr()),
                       "shasta_adam_prepare_f32")
-            self._armed[id(group)] = True
+            d["armed"] = True
+            d["count"] += 1
         return hip.ptr(d["dyn"])
+
+    def _check_step(self, gi, p, device):
+        """capturable: one counter serves the whole group, so a tensor about to be stepped must stand at the counter's step number
+        (a parameter that sat out some steps, or a hand-edited state, would silently get another step's bias correction)."""
+        if not self.capturable or torch.cuda.is_current_stream_capturing():
+            return
+        d = self._dev(gi, device)
+        at, have = d["count"] - (1 if d["armed"] else 0), int(self.state[p]["step"]) if self.state.get(p) else 0
+        if have != at:
+            group = self.param_groups[gi]
+            i = next(i for i, q in enumerate(group["params"]) if q is p)
+            raise hip.ShastaHipError("FusedAdam(capturable=True): param_groups[%d]['params'][%d] (shape %s) is at step %d, the group's "
+                                     "counter at step %d: one device-side counter cannot serve both (use capturable=False)"
+                                     % (gi, i, tuple(p.shape), have, at))
+
+    def load_state_dict(self, state_dict):
+        """torch's load, then: the moments are written INTO the tensors this optimizer already holds (same shape, dtype and device) and
+        every existing device counter is set in place from the loaded state['step'] - a graph captured earlier (GraphedTrainStep) keeps
+        those addresses, and a counter left at its old value would bias-correct the loaded moments as another step's."""
+        old = {p: st for p, st in self.state.items() if st}
+        super().load_state_dict(state_dict)
+        for p, o in old.items():
+            st = self.state[p]
+            if not st:  # no entry in the checkpoint = never stepped: zero moments, in the tensors already in use
+                st["step"] = 0
+            for k in ("exp_avg", "exp_avg_sq"):
+                t, n = o.get(k), st.get(k)
+                if n is None:
+                    st[k] = t.zero_()
+                elif t is not None and t is not n and t.shape == n.shape and t.dtype == n.dtype and t.device == n.device:
+                    st[k] = t.copy_(n)
+        for st in self.state.values():
+            if st:
+                st["step"] = int(st["step"])
+        for gi, d in self._dev_state.items():
+            self._seed(d, self._group_step(self.param_groups[gi]))
+        self.sync_hyper()
+
+    def _books(self):
+        """The host's step numbers (GraphedTrainStep: the capture pass runs step() without applying an update)."""
+        return {p: st["step"] for p, st in self.state.items() if st}, {gi: d["count"] for gi, d in self._dev_state.items()}
+
+    def _restore_books(self, books):
+        """Undo the host's counting since _books(); returns the parameters and groups that were counted (= stepped by the captured graph)."""
+        steps, counts = books
+        moved = [p for p, st in self.state.items() if st and st["step"] != steps.get(p, 0)]
+        for p in moved:
+            self.state[p]["step"] = steps.get(p, 0)
+        groups = [gi for gi, d in self._dev_state.items() if d["count"] != counts.get(gi, 0)]
+        for gi in groups:
+            self._dev_state[gi]["count"] = counts.get(gi, 0)
+        return moved, groups
+
+    def _count_replay(self, moved):
+        """A replayed graph advanced the device counters and updated these parameters: keep the host's numbers in step (no device sync)."""
+        params, groups = moved
+        for p in params:
+            self.state[p]["step"] += 1
+        for gi in groups:
+            self._dev_state[gi]["count"] += 1
 
     @torch.no_grad()
     def step_in_backward(self, p, factors, gdx, ldgdx, rdx, y, ldy):
         """The Adam update of matrix p from the factors of its gradient, and y (+)= gdx . p (p before the update), in one pass."""
-        group = next((g for g in self.param_groups if any(q is p for q in g["params"])), None)
-        if group is None:
+        gi = next((i for i, g in enumerate(self.param_groups) if any(q is p for q in g["params"])), None)
+        if gi is None:
             raise hip.ShastaHipError("FusedAdam(in_backward=True): the matrix is not one of this optimizer's parameters")
+        group = self.param_groups[gi]
         lib = hip.load()
+        self._check_step(gi, p, p.device)
         st = self._state_of(p)
         st["step"] = int(st["step"]) + 1
         G, ldg, X, ldx, R = factors
@@ -678,7 +757,7 @@ class FusedAdam(torch.optim.Optimizer):
         hip.check(lib.shasta_adam_lowrank_dx_f32(hip.ptr(p), hip.ptr(st["exp_avg"]), hip.ptr(st["exp_avg_sq"]), H, K, hip.ptr_view(G), ldg,
                                                  hip.ptr_view(X), ldx, R, hip.ptr_view(gdx), ldgdx, rdx, hip.ptr_view(y), ldy, 1, hip.ptr(ws), nb,
                                                  float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
-                                                 st["step"], self._dyn(group, p.device), hip.stream_ptr()), "shasta_adam_lowrank_dx_f32")
+                                                 st["step"], self._dyn(gi, p.device), hip.stream_ptr()), "shasta_adam_lowrank_dx_f32")
         torch.autograd.graph.increment_version(p)
 
     @torch.no_grad()
@@ -688,8 +767,12 @@ class FusedAdam(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         lib = hip.load()
-        for group in self.param_groups:
+        for gi, group in enumerate(self.param_groups):
             b1, b2 = group["betas"]
+            if self.capturable:  # before anything is counted or launched: a refused step changes nothing
+                for p in group["params"]:
+                    if p.is_cuda and (p.grad is not None or "_shasta_grad_factors" in p.__dict__):
+                        self._check_step(gi, p, p.device)
             small = {}  # step count -> the small tensors that share it: one launch for all of them (shasta_adam_multi_f32)
             for p in group["params"]:
                 factors = p.__dict__.pop("_shasta_grad_factors", None)
@@ -703,7 +786,7 @@ class FusedAdam(torch.optim.Optimizer):
                     G, ldg, X, ldx, R = factors
                     hip.check(lib.shasta_adam_lowrank_f32(hip.ptr(p), hip.ptr(st["exp_avg"]), hip.ptr(st["exp_avg_sq"]), p.shape[0], p.shape[1],
                                                           hip.ptr_view(G), ldg, hip.ptr_view(X), ldx, R, float(group["lr"]), float(b1), float(b2),
-                                                          float(group["eps"]), float(group["weight_decay"]), st["step"], self._dyn(group, p.device),
+                                                          float(group["eps"]), float(group["weight_decay"]), st["step"], self._dyn(gi, p.device),
                                                           hip.stream_ptr()), "shasta_adam_lowrank_f32")
                     torch.autograd.graph.increment_version(p)
                     continue
@@ -717,7 +800,7 @@ class FusedAdam(torch.optim.Optimizer):
                     g = g.clone()
                 hip.check(lib.shasta_adam_step_f32(hip.ptr(p), hip.ptr(g), hip.ptr(st["exp_avg"]), hip.ptr(st["exp_avg_sq"]), p.numel(),
                                                    float(group["lr"]), float(b1), float(b2), float(group["eps"]),
-                                                   float(group["weight_decay"]), st["step"], self._dyn(group, p.device), hip.stream_ptr()),
+                                                   float(group["weight_decay"]), st["step"], self._dyn(gi, p.device), hip.stream_ptr()),
                           "shasta_adam_step_f32")
                 # the kernel wrote through the raw pointer: tell torch (Shasta._ensure_packed and the conv-weight cache key
                 # their packed copies on (data_ptr, _version); autograd's saved-tensor checks rely on it too)
@@ -727,10 +810,11 @@ class FusedAdam(torch.optim.Optimizer):
                 arr = lambda j: (C.c_void_p * k)(*[it[j].data_ptr() for it in items])  # noqa: E731
                 hip.check(lib.shasta_adam_multi_f32(k, arr(0), arr(1), arr(2), arr(3), (C.c_long * k)(*[it[0].numel() for it in items]),
                                                     float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
-                                                    step_no, self._dyn(group, items[0][0].device), hip.stream_ptr()), "shasta_adam_multi_f32")
+                                                    step_no, self._dyn(gi, items[0][0].device), hip.stream_ptr()), "shasta_adam_multi_f32")
                 for it in items:
                     torch.autograd.graph.increment_version(it[0])
-            self._armed[id(group)] = False  # the next optimizer step prepares its own factors
+            if gi in self._dev_state:
+                self._dev_state[gi]["armed"] = False  # the next optimizer step prepares its own factors
         return loss
 
 
@@ -746,6 +830,10 @@ class GraphedTrainStep:
 
         step = GraphedTrainStep(model, opt, bev, pbev, det, prev, gt)        # three eager warm-up steps + the capture (they DO update the weights)
         for batch in loader: loss = step(*batch); scheduler.step()
+
+    The warm-up steps count as optimizer steps, the capture pass (which applies no update) does not, and every replay adds one to
+    state[p]['step'] on the host, so opt.state_dict() is a checkpoint at any time; opt.load_state_dict() writes into the counter, the
+    schedule values and the moments that the graph points at, and the same object goes on replaying.
     """
 
     def __init__(self, model, opt, bev, pbev, det_boxes, prev_det_boxes, gt, from_neck=False, warmup=3):
@@ -778,8 +866,11 @@ class GraphedTrainStep:
                 body()
         torch.cuda.current_stream().wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
+        books = opt._books()
         with torch.cuda.graph(self.graph):
             self.loss = body()
+        # the capture pass ran step() on the host and applied no update: it does not count.  What it counted is what a replay steps.
+        self._stepped = opt._restore_books(books)
         self.steps = 0
 
     def __call__(self, bev, pbev, det_boxes, prev_det_boxes, gt):
@@ -789,6 +880,7 @@ class GraphedTrainStep:
         self.opt.sync_hyper()
         self.graph.replay()
         self.steps += 1
+        self.opt._count_replay(self._stepped)  # state['step'] follows the device counter: the host knows the count, no sync
         # the replayed kernels wrote the weights without the host noticing: whatever the host derived from them (packed copies, keyed
         # on version counters that only move at capture time) is dropped, so that an eager forward after training packs afresh
         self.model.invalidate_weights_cache()

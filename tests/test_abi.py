@@ -21,7 +21,7 @@ def test_header_symbols_are_exported_and_bound():
     for n in names:
         assert hasattr(lib, n), "library does not export " + n
         assert n in hip.SYMBOLS, "ctypes binding missing for " + n
-    assert lib.shasta_abi_version() == hip.ABI_VERSION == 15
+    assert lib.shasta_abi_version() == hip.ABI_VERSION == 16
     assert b"gfx950" in lib.shasta_build_info()
     # the library carries the hash of the sources it was built from; hip.load() refuses a stale one
     from shasta_amd import build

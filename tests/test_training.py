@@ -969,7 +969,7 @@ def test_capturable_adam_and_the_graphed_step_equal_the_eager_loop():
     for (k, p), (_, q) in zip(ref[0].named_parameters(), graphed[0].named_parameters()):
         assert float((p - q).abs().max()) <= 1e-6 * max(1.0, float(p.abs().max())), k
     # the device-side step counter moved with the replays; an eager forward after training sees the trained weights
-    assert int(graphed[1].param_groups[0]["_shasta_dev"]["step"]) == total
+    assert int(graphed[1].device_step(0)) == total
     graphed[0].eval()
     ref[0].eval()
     with torch.no_grad():
