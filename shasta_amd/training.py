@@ -2,16 +2,22 @@
 returns (matched1, matched2) that carry autograd history, so the reference's training loop
 (tools/nusc_shasta/train.py:198-218: masked NLL in both directions, Adam) runs unchanged on top of it.
 
-Forward = the inference kernels (identical values).  Backward (`_AffinityTrainFn.backward`) recomputes the activations it
-needs with the REFERENCE (dense) formulation of the pair MLPs - the pair tensor is materialised - and back-propagates
-with hand-written HIP kernels only: every nn.Linear through the strided matrix-core GEMM (dX = dY W, dW = dY^T X, fixed
-order split-K), everything else through csrc/train.hip.  No torch autograd op runs inside the Function; torch is used for
-buffer allocation.  Gradients flow to every parameter of rows 6-16 and to the NHWC BEV maps (so `shared_conv`, which stays
-a torch module in train() mode with batch statistics like the reference, trains through ordinary autograd).
-The first layer of each pair MLP is factorised over the table rows in both directions (forward UP[t] + UC[d], backward
-row/column sums of the hidden gradient), so the (B, T*D, 2F) pair tensor of the reference is not materialised in training
-either; only the narrow hidden activations (F/8, F/8+32, 32 floats per pair) are.  Checked against torch autograd of the CPU
-oracle (tests/test_training.py).
+Forward = the inference kernels (identical values).  Backward: `_AffinityTrainFn.backward` is the list of stages, in reverse
+forward order - softmaxes, aff, the three pair MLPs with the combine, the hand-designed residual, the aug_shape anchors, the
+aug_dets anchors, the hand-over of the aug_shape first-layer gradients, the gather - and each stage is a method of `_Backward`,
+which carries the sizes, the saved tensors and the four gradient tables.  The stages recompute the activations they need and
+back-propagate with hand-written HIP kernels only: every nn.Linear through the strided matrix-core GEMM (dX = dY W,
+dW = dY^T X, fixed order split-K), everything else through csrc/train.hip and csrc/pair_bwd.hip.  No torch autograd op runs
+inside the Function; torch is used for buffer allocation.  Gradients flow to every parameter of rows 6-16 and to the NHWC BEV
+maps (so `shared_conv`, which stays a torch module in train() mode with batch statistics like the reference, trains through
+ordinary autograd).
+The first layer of each pair MLP is factorised over the table rows in both directions (`_PairMlp`: forward UP[t] + UC[d],
+backward row/column sums of the hidden gradient), so the (B, T*D, 2F) pair tensor of the reference is not materialised in
+training; the later layers run per pair on chip (`_PairMlpOnChip`, only the MLP's output per pair is written) or, for other
+widths, dense over the pairs (`_PairMlpDense`: the narrow hidden activations, F/8, F/8+32, 32 floats per pair, are
+materialised).  How the 1 GB first-layer gradients of aug_shape leave the backward (dense, exchanged factors, factors for
+FusedAdam, stepped in place) is decided in one place, `_Backward.hand_over`.  Checked against torch autograd of the CPU oracle
+(tests/test_training.py).
 """
 import ctypes as C
 
@@ -107,6 +113,301 @@ class _Mlp:
         return grads, g
 
 
+class _PairMlp:
+    """One of the three pair MLPs in the backward.  This base is the first layer, factorised over the table rows in both directions;
+    the two subclasses recompute and back-propagate the later layers: forward() -> out (P, n_out), backward(gout) -> [(gW, gb), ...] in
+    layer order.  parts: the column blocks of the first layer, (source table, its row stride, width, gradient table) for the previous /
+    current side."""
+
+    def __init__(self, c, kind, layers, parts):
+        self.c, self.kind, self.parts, self.later = c, kind, parts, layers[1:]
+        self.w0, self.b0 = layers[0]
+        widths = [wd for side in parts for _, _, wd, _ in side]
+        self.offs = [sum(widths[:k]) for k in range(len(widths))]  # the column offsets of the parts inside W0
+
+    def tables(self):
+        """The first layer's two table products: UP (B*T, E) over the previous side's rows, UC (B*D, E) over the current side's
+        (bias in UC)."""
+        c, w0, offs = self.c, self.w0, self.offs
+        E, kin = w0.shape
+        UP, UC = torch.empty(c.R, E, device=c.dev), torch.empty(c.R, E, device=c.dev)
+        npart = len(self.parts[0])
+        for k in range(npart):  # the two sides have the same shapes: one launch for both (the parts of a side accumulate in turn)
+            (tp, ld, wd, _), (tc, _, _, _) = self.parts[0][k], self.parts[1][k]
+            _gemm_group(c.lib, [tp, tc], (ld, 1), [w0[:, offs[k]:], w0[:, offs[npart + k]:]], (kin, 1), c.R, E, wd, [UP, UC],
+                        biases=[None, self.b0] if k == 0 else None, accum=k > 0, bf16=c.bf)
+        return UP, UC
+
+    def backward_rows(self, gUP, gUC):
+        """gUP (B*T, E), gUC (B*D, E): the pre-activation's gradient summed over the detections / the tracks -> (gW0, gb0); table
+        gradients accumulated."""
+        c, w0, offs = self.c, self.w0, self.offs
+        E, kin = w0.shape
+        gW0, gb0 = torch.empty_like(w0), torch.empty_like(self.b0)
+        _colsum(c.lib, gUC, E, c.R, E, gb0, c.ws)
+        npart = len(self.parts[0])
+        for k in range(npart):  # both sides per launch (distinct column blocks of gW0, distinct gradient tables)
+            (tp, ld, wd, gtp), (tc, _, _, gtc) = self.parts[0][k], self.parts[1][k]
+            cp, cc = offs[k], offs[npart + k]
+            _gemm_group(c.lib, [gUP, gUC], (1, E), [tp, tc], (1, ld), E, wd, c.R, [gW0[:, cp:], gW0[:, cc:]], ldc=kin, ws=c.ws, bf16=c.bf)   # dW0 block = gU^T X
+            _gemm_group(c.lib, [gUP, gUC], (E, 1), [w0[:, cp:], w0[:, cc:]], (1, kin), c.R, wd, E, [gtp, gtc], ldc=ld, accum=True, bf16=c.bf)  # dX += gU W0 block
+        return gW0, gb0
+
+
+class _PairMlpOnChip(_PairMlp):
+    """The later layers recomputed and back-propagated per pair on chip in fp32 (csrc/pair_bwd.hip): per pair only the MLP's output is
+    written and its gradient read; train_precision = "bf16" then shows in the GEMMs around them (first-layer tables, aff)."""
+
+    def forward(self):
+        c, lib = self.c, self.c.lib
+        self.UP, self.UC = self.tables()
+        self.later_t = [t for wb in self.later for t in wb] + [None] * (6 - 2 * len(self.later))  # (the tensors kept alive)
+        self.wts = (C.c_void_p * 6)(*[None if t is None else t.data_ptr() for t in self.later_t])
+        out = torch.empty(c.P, self.later[-1][0].shape[0], device=c.dev)
+        hip.check(lib.shasta_pair_mlp_forward_f32(self.kind, c.F, hip.ptr(self.UP), hip.ptr(self.UC), self.wts, c.B, c.T, c.D, hip.ptr(out),
+                                                  hip.stream_ptr()), "shasta_pair_mlp_forward_f32")
+        return out
+
+    def backward(self, gout):
+        c, lib, E = self.c, self.c.lib, self.w0.shape[0]
+        nb = lib.shasta_pair_mlp_workspace_bytes(self.kind, c.F, c.B, c.T, c.D)
+        pws = torch.empty((nb + 3) // 4, device=c.dev)
+        gUP, gUC = torch.empty(c.R, E, device=c.dev), torch.empty(c.R, E, device=c.dev)
+        img = torch.empty(lib.shasta_pair_mlp_grad_floats(self.kind, c.F), device=c.dev)
+        hip.check(lib.shasta_pair_mlp_backward_f32(self.kind, c.F, hip.ptr(self.UP), hip.ptr(self.UC), self.wts, hip.ptr(gout), c.B, c.T, c.D,
+                                                   hip.ptr(gUP), hip.ptr(gUC), hip.ptr(img), hip.ptr(pws), nb, hip.stream_ptr()),
+                  "shasta_pair_mlp_backward_f32")
+        tail_grads, o = [], 0
+        for w_, b_ in self.later:  # the image: [gW2 | gb2 | gW3 | gb3 | gW4 | gb4]
+            tail_grads.append((img[o:o + w_.numel()].view_as(w_), img[o + w_.numel():o + w_.numel() + b_.numel()]))
+            o += w_.numel() + b_.numel()  # (views at any 4-byte offset: FusedAdam updates small tensors without alignment demands)
+        return [self.backward_rows(gUP, gUC)] + tail_grads
+
+
+class _PairMlpDense(_PairMlp):
+    """The dense formulation (other widths than F = 64 | 256 | 320, Shasta.dense_pair_backward): hidden activations of every pair
+    materialised, strided GEMMs (bf16 operands there too under the option)."""
+
+    def forward(self):
+        c = self.c
+        UP, UC = self.tables()
+        E = UP.shape[1]
+        H = torch.empty(c.P, E, device=c.dev)  # H = relu(UP[t] + UC[d])
+        hip.check(c.lib.shasta_pair_hidden_f32(hip.ptr(UP), E, hip.ptr(UC), E, c.B, c.T, c.D, E, hip.ptr(H), hip.stream_ptr()), "shasta_pair_hidden_f32")
+        self.tail = _Mlp(c.lib, self.later, c.ws, bf16=c.bf)
+        return self.tail.forward(H, E, c.P)
+
+    def backward(self, gout):
+        c, E = self.c, self.w0.shape[0]
+        tail_grads, gZ = self.tail.backward(gout, mask_input=True)  # gZ (P, E): gradient of the first layer's pre-activation
+        gUP, gUC = torch.empty(c.R, E, device=c.dev), torch.empty(c.R, E, device=c.dev)
+        hip.check(c.lib.shasta_pair_reduce_f32(hip.ptr(gZ), c.B, c.T, c.D, E, hip.ptr(gUP), hip.ptr(gUC), hip.stream_ptr()), "shasta_pair_reduce_f32")
+        return [self.backward_rows(gUP, gUC)] + tail_grads
+
+
+class _Backward:
+    """What the stages of _AffinityTrainFn.backward share - the library, the sizes, the split-K scratch, the tensors the forward saved and
+    the four gradient tables (features and boxes of both frames) that the stages accumulate into - and the stages themselves, in the
+    order backward() calls them.  A stage takes what it needs and returns what it produces; its temporaries die with it."""
+
+    def __init__(self, model, S):
+        self.model, self.S, self.lib = model, S, hip.load()
+        self.dev = dev = S["m1"].device
+        B, N, F = S["m1"].shape[0], model.max_obj, model.aug_shape_output
+        T = N + 2  # table rows: the objects and the two anchors, on both sides (T tracks, D detections)
+        self.B, self.N, self.T, self.D, self.F, self.nf = B, N, T, T, F, model.num_feats
+        self.Dp, self.R, self.P = (T + 3) // 4 * 4, B * T, B * T * T
+        self.ws = torch.empty(64 * 1024 * 1024 // 4, device=dev)  # split-K scratch
+        # BASELINE config 5's reduced-precision option: the GEMMs of `aff` and of the pair MLPs' first-layer tables (recomputation and
+        # gradients) take bf16 operands with fp32 accumulation; parameters, their gradients, Adam and the anchor MLPs stay fp32
+        self.bf = getattr(model, "train_precision", "fp32") == "bf16"
+        self.dfeat, self.dprev_feat = torch.zeros(B, T, F, device=dev), torch.zeros(B, T, F, device=dev)
+        self.ddet_tab, self.dprev_tab = torch.zeros(B, T, 8, device=dev), torch.zeros(B, T, 8, device=dev)
+
+    def softmaxes(self, g1, g2):
+        """shasta.py:324-325 -> gm (B*T, Dp)"""
+        S, g1, g2 = self.S, g1.contiguous().float(), g2.contiguous().float()
+        gm = torch.empty(self.R, self.Dp, device=self.dev)
+        hip.check(self.lib.shasta_softmax_bwd_f32(hip.ptr(S["m1"]), hip.ptr(g1), hip.ptr(S["m2"]), hip.ptr(g2), self.B, self.N, hip.ptr(gm), self.Dp,
+                                                  hip.stream_ptr()), "shasta_softmax_bwd_f32")
+        return gm
+
+    def aff(self, gm):
+        """aff (shasta.py:323): recompute the hidden activations, then back-propagate -> its gradients, gres (B*T, Dp)"""
+        model, D = self.model, self.D
+        residual = self.S["residual"].reshape(self.R, D).contiguous()
+        aff = _Mlp(self.lib, [(model.aff[k].weight.detach(), model.aff[k].bias.detach()) for k in (0, 2, 4, 6, 8, 10)], self.ws, bf16=self.bf)
+        aff.forward(residual, D, self.R)
+        return aff.backward(gm[:, :D].contiguous(), need_gx=True, gx_ld=self.Dp)
+
+    def pair_mlps(self, gres):
+        """The three pair MLPs and the combine (shasta.py:286-316): first layers factorised over the table rows, later layers per pair on
+        chip or dense -> gradients of fuse_shape, res_coeff, fuse_det; gdist and denom for the hand-designed residual."""
+        model, S, lib, dev, B, T, D, Dp, F, nf = self.model, self.S, self.lib, self.dev, self.B, self.T, self.D, self.Dp, self.F, self.nf
+        pf, cf, pt, ct = S["prev_feat"], S["feat"], S["prev_tab"], S["det_tab"]
+        feats = ([(pf, F, F, self.dprev_feat)], [(cf, F, F, self.dfeat)])
+        tabs = ([(pt, 8, nf, self.dprev_tab)], [(ct, 8, nf, self.ddet_tab)])
+        lin = lambda m, ks: [(m[k].weight.detach(), m[k].bias.detach()) for k in ks]  # noqa: E731
+        on_chip = bool(lib.shasta_pair_mlp_supported(F)) and not getattr(model, "dense_pair_backward", False)
+        Pair = _PairMlpOnChip if on_chip else _PairMlpDense
+        mlps = [Pair(self, 0, lin(model.fuse_shape, (0, 2, 4, 6)), feats),
+                Pair(self, 2, lin(model.res_coeff, (0, 2, 4)), (feats[0] + tabs[0], feats[1] + tabs[1])),
+                Pair(self, 1, lin(model.fuse_det, (0, 2, 4)), tabs)]
+        shape, coeff, fused = [m.forward() for m in mlps]  # (P,1), (P,3), (P,1)
+        dist = torch.empty(B * T, Dp, device=dev)
+        denom = torch.empty(2 * B * D, device=dev)
+        hip.check(lib.shasta_hand_dist_f32(hip.ptr(pt), hip.ptr(ct), B, T, D, nf, hip.ptr(dist), Dp, hip.ptr(denom), hip.stream_ptr()),
+                  "shasta_hand_dist_f32")
+        gcoeff, gfused, gshape = torch.empty(self.P, 3, device=dev), torch.empty(self.P, 1, device=dev), torch.empty(self.P, 1, device=dev)
+        gdist = torch.zeros(B * T, Dp, device=dev)
+        hip.check(lib.shasta_combine_bwd_f32(hip.ptr(gres), hip.ptr(coeff), 3, hip.ptr(fused), 1, hip.ptr(shape), 1, hip.ptr(dist), B, T, D, Dp,
+                                             hip.ptr(gcoeff), hip.ptr(gfused), hip.ptr(gshape), hip.ptr(gdist), hip.stream_ptr()),
+                  "shasta_combine_bwd_f32")
+        fs_grads, rc_grads, fd_grads = [m.backward(g) for m, g in zip(mlps, (gshape, gcoeff, gfused))]
+        return fs_grads, rc_grads, fd_grads, gdist, denom
+
+    def hand_residual(self, gdist, denom):
+        """hand-designed residual -> anchor boxes (rows N, N+1 of both tables)"""
+        S = self.S
+        hip.check(self.lib.shasta_hand_dist_bwd_f32(hip.ptr(gdist), self.Dp, hip.ptr(S["prev_tab"]), hip.ptr(S["det_tab"]), hip.ptr(denom), self.B,
+                                                    self.T, self.D, self.nf, self.N, 2, hip.ptr(self.dprev_tab), hip.ptr(self.ddet_tab),
+                                                    hip.stream_ptr()), "shasta_hand_dist_bwd_f32")
+
+    def anchor_dw1(self, gh, xs, sx_m, K, w1s):
+        """dW1 = ghid^T x of the four MLPs of an anchor kind: gh their (B, H) column blocks of ghid, xs their input rows at stride sx_m"""
+        B, H, ldg = self.B, w1s[0].shape[0], gh[0].stride(0)
+        gW1s = [torch.empty_like(w) for w in w1s]
+        if B <= 16 and K % 4 == 0 and sx_m % 4 == 0:  # rank-B updates: the streaming kernel, one pass over each output
+            for i in range(len(w1s)):
+                _outer(self.lib, gh[i], ldg, xs[i], sx_m, B, H, K, gW1s[i])
+        else:
+            _gemm_group(self.lib, gh, (1, ldg), xs, (1, sx_m), H, K, B, gW1s)
+        return gW1s
+
+    def anchors(self, seqs, xs, sx_m, K, g_list, c0, c1, hid_cat=None, defer_w1=False):
+        """Anchor MLPs (shasta.py:241-247, 260-267), the four of a kind at once (they are equal in shape): seqs = Sequential(Linear, ReLU,
+        Linear) each, xs their input rows at stride sx_m, g_list (B, out) gradients of the |.| outputs (columns c0:c1 are the ones under
+        |.|).  Every nn.Linear product of the four in ONE launch (shasta_gemm_strided_group_f32), hidden activations / their gradients /
+        the pre-|.| outputs side by side in (B, 4 H) and (B, 4 out) matrices so that one abs and one column-sum launch serve all four.
+        hid_cat: the hidden activations when the forward kept them (recomputed otherwise); defer_w1: leave the first layers' weight
+        gradients to the caller (None), who gets their factor.  Returns ((gW1, gb1, gW2, gb2) per MLP, ghid blocks, ghid)."""
+        lib, dev, B, ws, n, st = self.lib, self.dev, self.B, self.ws, len(seqs), hip.stream_ptr
+        w1s, b1s = [q[0].weight.detach() for q in seqs], [q[0].bias.detach() for q in seqs]
+        w2s, b2s = [q[2].weight.detach() for q in seqs], [q[2].bias.detach() for q in seqs]
+        H, nout = w1s[0].shape[0], w2s[0].shape[0]
+        if H == 0:  # aug_dets at max_obj <= 4: no hidden unit, the anchor is |bias| and gb2 the only gradient that is not empty
+            pre = torch.stack([b.expand(B, nout) for b in b2s])  # (4, B, out), one MLP after the other: each column sum as it runs alone
+            g_all, gpre, gb2 = torch.stack(g_list), torch.empty_like(pre), torch.empty(n, nout, device=dev)
+            hip.check(lib.shasta_abs_f32(hip.ptr(pre), hip.ptr(g_all), hip.ptr(gpre), B * n * nout, nout, c0, c1, 1, st()), "shasta_abs_f32")
+            for i in range(n):
+                _colsum(lib, gpre[i], nout, B, nout, gb2[i], ws)
+            return [(torch.zeros_like(w1s[i]), torch.zeros_like(b1s[i]), torch.zeros_like(w2s[i]), gb2[i]) for i in range(n)], None, None
+        blocks = lambda t, w: [t[:, i * w:(i + 1) * w] for i in range(n)]  # noqa: E731
+        if hid_cat is None:
+            hid_cat = torch.empty(B, n * H, device=dev)
+            _gemm_group(lib, xs, (sx_m, 1), w1s, (K, 1), B, H, K, blocks(hid_cat, H), ldc=n * H, biases=b1s, act=1, ws=ws)  # (few rows, long K: split)
+        hids = blocks(hid_cat, H)
+        pre = torch.empty(B, n * nout, device=dev)
+        _gemm_group(lib, hids, (n * H, 1), w2s, (H, 1), B, nout, H, blocks(pre, nout), ldc=n * nout, biases=b2s, ws=ws)
+        g_cat = torch.cat(g_list, dim=1)
+        gpre = torch.empty_like(pre)
+        hip.check(lib.shasta_abs_f32(hip.ptr(pre), hip.ptr(g_cat), hip.ptr(gpre), B * n * nout, nout, c0, c1, 1, st()), "shasta_abs_f32")
+        gb2 = torch.empty(n * nout, device=dev)
+        _colsum(lib, gpre, n * nout, B, n * nout, gb2, ws)
+        gpres = blocks(gpre, nout)
+        gW2 = torch.empty(n, nout, H, device=dev)
+        _gemm_group(lib, gpres, (1, n * nout), hids, (1, n * H), nout, H, B, [gW2[i] for i in range(n)])
+        ghid = torch.empty(B, n * H, device=dev)
+        gh = blocks(ghid, H)
+        _gemm_group(lib, gpres, (n * nout, 1), w2s, (1, H), B, H, nout, gh, ldc=n * H, masks=hids, ldmask=n * H)
+        gb1 = torch.empty(n * H, device=dev)
+        _colsum(lib, ghid, n * H, B, n * H, gb1, ws)
+        gW1s = [None] * n if defer_w1 else self.anchor_dw1(gh, xs, sx_m, K, w1s)
+        return [(gW1s[i], gb1[i * H:(i + 1) * H], gW2[i], gb2[i * nout:(i + 1) * nout]) for i in range(n)], gh, ghid
+
+    def shape_anchors(self):
+        """aug_shape[i]: input = rows < N of feat (i<2) / prev_feat (i>=2); output row N + (i&1) of prev_feat (i<2) / feat (i>=2).  The
+        hidden width N*F/64 = N*num_point is never 0; the first layers' weight gradients are left to hand_over()."""
+        S, N, T, F = self.S, self.N, self.T, self.F
+        gout = [(self.dprev_feat if i < 2 else self.dfeat)[:, N + (i & 1), :] for i in range(4)]
+        return self.anchors([self.model.aug_shape[i] for i in range(4)], [S["feat"], S["feat"], S["prev_feat"], S["prev_feat"]], T * F, N * F, gout,
+                            0, F, hid_cat=S["shape_hidden"], defer_w1=True)
+
+    def box_anchors(self):
+        """aug_dets[i]: input = boxes[:, :, :7] before back-projection (det for i<2, prev for i>=2), output anchor box row"""
+        S, N = self.S, self.N
+        xb_det, xb_prev = S["det_pre"][:, :, :7].contiguous(), S["prev"][:, :, :7].contiguous()
+        gout = [(self.dprev_tab if i < 2 else self.ddet_tab)[:, N + (i & 1), :7] for i in range(4)]
+        return self.anchors([self.model.aug_dets[i] for i in range(4)], [xb_det, xb_det, xb_prev, xb_prev], 7 * N, 7 * N, gout, 3, 6)[0]
+
+    def hand_over(self, shape_grads, ghids, ghid_cat, need_dx):
+        """How the gradients of the four aug_shape first layers ((N*F/64, N*F) each, 1 GB at N = 500) leave the backward - as a dense
+        gradient, as the average over the ranks formed from exchanged factors, as factors for FusedAdam, or already applied - and the
+        dx = ghid W1 they owe the feature tables.  ghids / ghid_cat: the hidden gradients of shape_anchors(); need_dx per MLP.
+        Returns shape_grads with the weight gradients filled in (None where .grad stays None)."""
+        model, S, lib, dev, B, N, T, F, st = self.model, self.S, self.lib, self.dev, self.B, self.N, self.T, self.F, hip.stream_ptr
+        Hs_, K = N * F // 64, N * F
+        w1ps = [model.aug_shape[i][0].weight for i in range(4)]
+        w1s = [p.detach() for p in w1ps]
+        xs, gins = [S["feat"], S["feat"], S["prev_feat"], S["prev_feat"]], [self.dfeat, self.dfeat, self.dprev_feat, self.dprev_feat]
+        # Data-parallel training: dW1 of an aug_shape MLP is ghid^T x, a rank-B update of a (N*F/64, N*F) matrix (1 GB at
+        # N=500).  Instead of all-reducing 4 x 1 GB of gradients, the ranks exchange the FACTORS (all_gather of B x (4H + 2K)
+        # floats per rank, ~1 MB per frame-pair) and every rank forms the averaged gradient with one GEMM over world*B rows.
+        for p_ in w1ps:  # a stale flag from a step reduced some other way
+            p_._shasta_grad_is_global = False
+        world, group, exchange, lowrank, stepper = first_layer_plan(model, B, K)
+        if world > 1:
+            _check_equal_local_batch(B, world, group, dev)
+        # FusedAdam(..., in_backward=True): the optimizer steps the four matrices HERE, in the pass that also forms dx = ghid W1 (with the
+        # weights as they are before the update): the 1 GB matrix is read once for both (shasta_adam_lowrank_dx_f32)
+        in_bwd = lowrank and stepper is not None and stepper.in_backward and world * B <= 64 and B <= 16 and K >= 4
+        gW1s = [None] * 4 if exchange or lowrank else self.anchor_dw1(ghids, xs, T * F, K, w1s)
+        # dx = ghid W1 into the rows < N of the input table's gradient feeds the gather's backward only: skipped for a map whose gradient
+        # nobody asked for (features from a frozen pipeline; autograd's needs_input_grad), with the gather's backward itself
+        if not in_bwd and any(need_dx):
+            if B <= 16 and K % 4 == 0:  # small batch: stream the 1 GB matrix once (csrc/train.hip)
+                for i in (j for j in range(4) if need_dx[j]):
+                    nb = lib.shasta_smallm_nn_workspace_bytes(B, Hs_, K)
+                    sws = torch.empty((nb + 3) // 4, device=dev)
+                    hip.check(lib.shasta_smallm_nn_f32(hip.ptr_view(ghids[i]), ghids[i].stride(0), hip.ptr(w1s[i]), B, Hs_, K, hip.ptr(gins[i]),
+                                                       T * F, 1, hip.ptr(sws), nb, st()), "shasta_smallm_nn_f32")
+            else:  # two MLPs add into each table: one launch for the first of each pair, one for the second
+                for pair in ((0, 2), (1, 3)):
+                    pair = [i for i in pair if need_dx[i]]
+                    if pair:
+                        _gemm_group(lib, [ghids[i] for i in pair], (ghids[0].stride(0), 1), [w1s[i] for i in pair], (1, K), B, K, Hs_,
+                                    [gins[i] for i in pair], ldc=T * F, accum=True)
+        if exchange:
+            gh_all = _all_gather_rows(ghid_cat, world, group)                                                     # (world*B, 4H)
+            xg = [_all_gather_rows(S[k][:, :N, :].reshape(B, K), world, group) for k in ("feat", "prev_feat")]  # (world*B, K)
+            hip.check(lib.shasta_scale_f32(hip.ptr(gh_all), gh_all.numel(), 1.0 / world, st()), "shasta_scale_f32")
+            for i, w1p in enumerate(w1ps):
+                if lowrank:  # (the parameter's .grad stays None; allreduce_gradients skips it)
+                    w1p._shasta_grad_factors = (gh_all[:, i * Hs_:], 4 * Hs_, xg[0 if i < 2 else 1], K, world * B)
+                    continue
+                gW1s[i] = torch.empty_like(w1p)
+                _outer(lib, gh_all[:, i * Hs_:], 4 * Hs_, xg[0 if i < 2 else 1], K, world * B, Hs_, K, gW1s[i])
+                w1p._shasta_grad_is_global = True  # allreduce_gradients must not reduce it again
+        elif lowrank:
+            for i, w1p in enumerate(w1ps):  # one rank: the local factors as they are (the input rows lie T * F apart in the feature table)
+                w1p._shasta_grad_factors = (ghids[i], ghids[i].stride(0), xs[i], T * F, B)
+        if in_bwd:
+            for i in (j for j in range(4) if need_dx[j]):  # (a matrix whose dx nobody needs keeps its factors for step())
+                stepper.step_in_backward(w1ps[i], w1ps[i].__dict__.pop("_shasta_grad_factors"), ghids[i], ghids[i].stride(0), B, gins[i], T * F)
+        return [(gW1s[i],) + g[1:] for i, g in enumerate(shape_grads)]
+
+    def gather(self, gtab, boxes):
+        """gather (shasta.py:231-238) -> gradient of one NHWC map"""
+        model, N, F, T = self.model, self.N, self.F, self.T
+        Bb, H_, W_, Cc = self.S["bev_shape"]
+        dbev = torch.zeros(Bb, H_, W_, Cc, device=self.dev)
+        x0, y0, vx, vy, stv = model.bev_extractor._geom()
+        hip.check(self.lib.shasta_bev_gather_bwd_f32(hip.ptr(gtab), self.B, H_, W_, Cc, hip.ptr(boxes), N, boxes.shape[2], N * boxes.shape[2],
+                                                     model.num_point, x0, y0, vx, vy, stv, F, T * F, hip.ptr(dbev), hip.stream_ptr()),
+                  "shasta_bev_gather_bwd_f32")
+        return dbev
+
+
 class _AffinityTrainFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, bev, prev_bev, det_boxes, prev_det_boxes, *params):
@@ -122,332 +423,20 @@ class _AffinityTrainFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g1, g2):
-        model, S = ctx.model, ctx.saved
-        lib = hip.load()
-        dev = S["m1"].device
-        B, N = S["m1"].shape[0], model.max_obj
-        T = D = N + 2
-        F, nf = model.aug_shape_output, model.num_feats
-        Dp = (D + 3) // 4 * 4
-        P = B * T * D
-        ws = torch.empty(64 * 1024 * 1024 // 4, device=dev)  # split-K scratch
-        # BASELINE config 5's reduced-precision option: the GEMMs of `aff` and of the pair MLPs' first-layer tables (recomputation and
-        # gradients) take bf16 operands with fp32 accumulation; parameters, their gradients, Adam and the anchor MLPs stay fp32
-        bf = getattr(model, "train_precision", "fp32") == "bf16"
-        st = hip.stream_ptr
-        g1 = g1.contiguous().float()
-        g2 = g2.contiguous().float()
-
-        # ---- softmaxes (shasta.py:324-325) ----
-        gm = torch.empty(B * T, Dp, device=dev)
-        hip.check(lib.shasta_softmax_bwd_f32(hip.ptr(S["m1"]), hip.ptr(g1), hip.ptr(S["m2"]), hip.ptr(g2), B, N, hip.ptr(gm), Dp, st()),
-                  "shasta_softmax_bwd_f32")
-        # ---- aff (shasta.py:323): recompute the hidden activations, then back-propagate ----
-        residual = S["residual"].reshape(B * T, D).contiguous()
-        aff = _Mlp(lib, [(model.aff[k].weight.detach(), model.aff[k].bias.detach()) for k in (0, 2, 4, 6, 8, 10)], ws, bf16=bf)
-        aff.forward(residual, D, B * T)
-        gmc = gm[:, :D].contiguous()
-        aff_grads, gres = aff.backward(gmc, need_gx=True, gx_ld=Dp)  # gres (B*T, Dp)
-
-        # ---- pair MLPs (shasta.py:286-316): first layers factorised over the table rows, later layers dense over pairs ----
-        pf, cf, pt, ct = S["prev_feat"], S["feat"], S["prev_tab"], S["det_tab"]
-        dfeat = torch.zeros(B, T, F, device=dev)
-        dprev_feat = torch.zeros(B, T, F, device=dev)
-        ddet_tab = torch.zeros(B, T, 8, device=dev)
-        dprev_tab = torch.zeros(B, T, 8, device=dev)
-        # column blocks of each first layer: (source table, its row stride, width, gradient table) for the previous / current side
-        parts = {
-            "fs": ([(pf, F, F, dprev_feat)], [(cf, F, F, dfeat)]),
-            "rc": ([(pf, F, F, dprev_feat), (pt, 8, nf, dprev_tab)], [(cf, F, F, dfeat), (ct, 8, nf, ddet_tab)]),
-            "fd": ([(pt, 8, nf, dprev_tab)], [(ct, 8, nf, ddet_tab)]),
-        }
-        lin = lambda m, ks: [(m[k].weight.detach(), m[k].bias.detach()) for k in ks]  # noqa: E731
-        mods = {"fs": lin(model.fuse_shape, (0, 2, 4, 6)), "rc": lin(model.res_coeff, (0, 2, 4)), "fd": lin(model.fuse_det, (0, 2, 4))}
-        R = B * T
-
-        def first_layer_tables(name):
-            """The first layer's two table products: UP (B*T, E) over the previous side's rows, UC (B*D, E) over the current side's
-            (bias in UC); and the column offsets of the parts inside W0."""
-            w0, b0 = mods[name][0]
-            E, kin = w0.shape
-            UP, UC = torch.empty(R, E, device=dev), torch.empty(R, E, device=dev)
-            col, offs = 0, []
-            for side in (0, 1):
-                for _, _, wd, _ in parts[name][side]:
-                    offs.append(col)
-                    col += wd
-            npart = len(parts[name][0])
-            for k in range(npart):  # the two sides have the same shapes: one launch for both (the parts of a side accumulate in turn)
-                (tp, ld, wd, _), (tc, _, _, _) = parts[name][0][k], parts[name][1][k]
-                _gemm_group(lib, [tp, tc], (ld, 1), [w0[:, offs[k]:], w0[:, offs[npart + k]:]], (kin, 1), R, E, wd, [UP, UC],
-                            biases=[None, b0] if k == 0 else None, accum=k > 0, bf16=bf)
-            return UP, UC, offs
-
-        def first_layer(name):
-            """H (P, E) = relu(UP[t] + UC[d]); returns H and the column offsets of the parts inside W0."""
-            UP, UC, offs = first_layer_tables(name)
-            E = UP.shape[1]
-            H = torch.empty(P, E, device=dev)
-            hip.check(lib.shasta_pair_hidden_f32(hip.ptr(UP), E, hip.ptr(UC), E, B, T, D, E, hip.ptr(H), st()), "shasta_pair_hidden_f32")
-            return H, offs
-
-        def first_layer_bwd(name, gZ, offs):
-            """gZ (P, E) gradient of the first layer's pre-activation -> (gW0, gb0); table gradients accumulated."""
-            E = mods[name][0][0].shape[0]
-            gUP, gUC = torch.empty(R, E, device=dev), torch.empty(R, E, device=dev)
-            hip.check(lib.shasta_pair_reduce_f32(hip.ptr(gZ), B, T, D, E, hip.ptr(gUP), hip.ptr(gUC), st()), "shasta_pair_reduce_f32")
-            return first_layer_bwd_rows(name, gUP, gUC, offs)
-
-        def first_layer_bwd_rows(name, gUP, gUC, offs):
-            """gUP (B*T, E), gUC (B*D, E): the pre-activation's gradient summed over the detections / the tracks -> (gW0, gb0)."""
-            w0, b0 = mods[name][0]
-            E, kin = w0.shape
-            gW0, gb0 = torch.empty_like(w0), torch.empty_like(b0)
-            _colsum(lib, gUC, E, R, E, gb0, ws)
-            npart = len(parts[name][0])
-            for k in range(npart):  # both sides per launch (distinct column blocks of gW0, distinct gradient tables)
-                (tp, ld, wd, gtp), (tc, _, _, gtc) = parts[name][0][k], parts[name][1][k]
-                cp, cc = offs[k], offs[npart + k]
-                _gemm_group(lib, [gUP, gUC], (1, E), [tp, tc], (1, ld), E, wd, R, [gW0[:, cp:], gW0[:, cc:]], ldc=kin, ws=ws, bf16=bf)   # dW0 block = gU^T X
-                _gemm_group(lib, [gUP, gUC], (E, 1), [w0[:, cp:], w0[:, cc:]], (1, kin), R, wd, E, [gtp, gtc], ldc=ld, accum=True, bf16=bf)  # dX += gU W0 block
-            return gW0, gb0
-
-        # The later layers of a pair MLP.  Default (F = 64 | 256 | 320): recomputed and back-propagated per pair on chip in fp32
-        # (csrc/pair_bwd.hip) - per pair only the MLP's output is written and its gradient read; train_precision = "bf16" then shows in
-        # the GEMMs around them (first-layer tables, aff).  Otherwise (other widths, Shasta.dense_pair_backward): the dense formulation -
-        # hidden activations of every pair materialised, strided GEMMs (bf16 operands there too under the option).
-        on_chip = bool(lib.shasta_pair_mlp_supported(F)) and not getattr(model, "dense_pair_backward", False)
-        kinds = {"fs": 0, "fd": 1, "rc": 2}
-        tails, Hs, offs_, tabs, wts = {}, {}, {}, {}, {}
-        outs = {}
-        for name in ("fs", "rc", "fd"):
-            if on_chip:
-                UP_, UC_, offs_[name] = first_layer_tables(name)
-                tabs[name] = (UP_, UC_)
-                later = [t for wb in mods[name][1:] for t in wb] + [None] * (8 - 2 * len(mods[name]))
-                wts[name] = ((C.c_void_p * 6)(*[None if t is None else t.data_ptr() for t in later]), later)  # (the tensors kept alive)
-                outs[name] = torch.empty(P, mods[name][-1][0].shape[0], device=dev)
-                hip.check(lib.shasta_pair_mlp_forward_f32(kinds[name], F, hip.ptr(UP_), hip.ptr(UC_), wts[name][0], B, T, D,
-                                                          hip.ptr(outs[name]), st()), "shasta_pair_mlp_forward_f32")
-                continue
-            Hs[name], offs_[name] = first_layer(name)
-            tails[name] = _Mlp(lib, mods[name][1:], ws, bf16=bf)
-            outs[name] = tails[name].forward(Hs[name], Hs[name].shape[1], P)
-        shape, coeff, fused = outs["fs"], outs["rc"], outs["fd"]  # (P,1), (P,3), (P,1)
-        dist = torch.empty(B * T, Dp, device=dev)
-        denom = torch.empty(2 * B * D, device=dev)
-        hip.check(lib.shasta_hand_dist_f32(hip.ptr(pt), hip.ptr(ct), B, T, D, nf, hip.ptr(dist), Dp, hip.ptr(denom), st()),
-                  "shasta_hand_dist_f32")
-        gcoeff, gfused, gshape = torch.empty(P, 3, device=dev), torch.empty(P, 1, device=dev), torch.empty(P, 1, device=dev)
-        gdist = torch.zeros(B * T, Dp, device=dev)
-        hip.check(lib.shasta_combine_bwd_f32(hip.ptr(gres), hip.ptr(coeff), 3, hip.ptr(fused), 1, hip.ptr(shape), 1, hip.ptr(dist), B, T, D, Dp,
-                                             hip.ptr(gcoeff), hip.ptr(gfused), hip.ptr(gshape), hip.ptr(gdist), st()), "shasta_combine_bwd_f32")
-        pair_grads = {}
-        for name, gout in (("fs", gshape), ("rc", gcoeff), ("fd", gfused)):
-            if on_chip:
-                UP_, UC_ = tabs[name]
-                E = UP_.shape[1]
-                nb = lib.shasta_pair_mlp_workspace_bytes(kinds[name], F, B, T, D)
-                pws = torch.empty((nb + 3) // 4, device=dev)
-                gUP, gUC = torch.empty(R, E, device=dev), torch.empty(R, E, device=dev)
-                img = torch.empty(lib.shasta_pair_mlp_grad_floats(kinds[name], F), device=dev)
-                hip.check(lib.shasta_pair_mlp_backward_f32(kinds[name], F, hip.ptr(UP_), hip.ptr(UC_), wts[name][0], hip.ptr(gout), B, T, D,
-                                                           hip.ptr(gUP), hip.ptr(gUC), hip.ptr(img), hip.ptr(pws), nb, st()),
-                          "shasta_pair_mlp_backward_f32")
-                tail_grads, o = [], 0
-                for w_, b_ in mods[name][1:]:  # the image: [gW2 | gb2 | gW3 | gb3 | gW4 | gb4]
-                    tail_grads.append((img[o:o + w_.numel()].view_as(w_), img[o + w_.numel():o + w_.numel() + b_.numel()]))
-                    o += w_.numel() + b_.numel()  # (views at any 4-byte offset: FusedAdam updates small tensors without alignment demands)
-                pair_grads[name] = [first_layer_bwd_rows(name, gUP, gUC, offs_[name])] + tail_grads
-                del pws
-                continue
-            tail_grads, gZ = tails[name].backward(gout, mask_input=True)
-            pair_grads[name] = [first_layer_bwd(name, gZ, offs_[name])] + tail_grads
-            del gZ
-        fs_grads, rc_grads, fd_grads = pair_grads["fs"], pair_grads["rc"], pair_grads["fd"]
-        del Hs, tails, outs
-        # ---- hand-designed residual -> anchor boxes (rows N, N+1 of both tables) ----
-        hip.check(lib.shasta_hand_dist_bwd_f32(hip.ptr(gdist), Dp, hip.ptr(S["prev_tab"]), hip.ptr(S["det_tab"]), hip.ptr(denom), B, T, D, nf,
-                                               N, 2, hip.ptr(dprev_tab), hip.ptr(ddet_tab), st()), "shasta_hand_dist_bwd_f32")
-
-        # ---- anchor MLPs (shasta.py:241-247, 260-267) ----
-        def anchor_bwd(seq, x, sx_m, K, g_out, c0, c1, hid=None, defer_w1=False):
-            """seq = Sequential(Linear, ReLU, Linear); x rows at stride sx_m; g_out (B, out) gradient of the |.| output;
-            hid: the hidden activations when the forward kept them (recomputed otherwise); defer_w1: leave the first
-            layer's weight gradient to the caller (returned as None), who gets its factor ghid."""
-            w1, b1, w2, b2 = seq[0].weight.detach(), seq[0].bias.detach(), seq[2].weight.detach(), seq[2].bias.detach()
-            H, nout = w1.shape[0], w2.shape[0]
-            if hid is None:
-                hid = torch.empty(B, max(H, 1), device=dev)
-                if H > 0:
-                    _gemm(lib, x, (sx_m, 1), w1, (K, 1), B, H, K, hid, ldc=max(H, 1), bias=b1, act=1, ws=ws)  # (few rows, long K: split)
-            pre = torch.empty(B, nout, device=dev)
-            if H > 0:
-                _gemm(lib, hid, (max(H, 1), 1), w2, (H, 1), B, nout, H, pre, bias=b2, ws=ws)
-            else:
-                pre.copy_(b2.expand(B, nout))
-            gpre = torch.empty(B, nout, device=dev)
-            hip.check(lib.shasta_abs_f32(hip.ptr(pre), hip.ptr(g_out), hip.ptr(gpre), B * nout, nout, c0, c1, 1, st()), "shasta_abs_f32")
-            gb2 = torch.empty_like(b2)
-            _colsum(lib, gpre, nout, B, nout, gb2, ws)
-            gW2, gb1 = torch.zeros_like(w2), torch.zeros_like(b1)
-            gW1 = None if (defer_w1 and H > 0) else (torch.empty_like(w1) if H > 0 else torch.zeros_like(w1))
-            gx = None
-            if H > 0:
-                _gemm(lib, gpre, (1, nout), hid, (1, max(H, 1)), nout, H, B, gW2)
-                ghid = torch.empty(B, H, device=dev)
-                _gemm(lib, gpre, (nout, 1), w2, (1, H), B, H, nout, ghid, mask=hid, ldmask=max(H, 1))
-                if gW1 is not None:
-                    _outer(lib, ghid, H, x, sx_m, B, H, K, gW1)
-                _colsum(lib, ghid, H, B, H, gb1, ws)
-                gx = ghid
-            return (gW1, gb1, gW2, gb2), gx, w1
-
-        # Data-parallel training: dW1 of an aug_shape MLP is ghid^T x, a rank-B update of a (N*F/64, N*F) matrix (1 GB at
-        # N=500).  Instead of all-reducing 4 x 1 GB of gradients, the ranks exchange the FACTORS (all_gather of B x (4H + 2K)
-        # floats per rank, ~1 MB per frame-pair) and every rank forms the averaged gradient with one GEMM over world*B rows.
-        for p_ in (model.aug_shape[i][0].weight for i in range(4)):  # a stale flag from a step reduced some other way
-            p_._shasta_grad_is_global = False
-        world, group, exchange, lowrank, stepper = first_layer_plan(model, B, N * F)
-        if world > 1:
-            _check_equal_local_batch(B, world, group, dev)
-        # FusedAdam(..., in_backward=True): the optimizer steps the four matrices HERE, in the pass that also forms dx = ghid W1 (with the
-        # weights as they are before the update): the 1 GB matrix is read once for both (shasta_adam_lowrank_dx_f32)
-        in_bwd = lowrank and stepper is not None and stepper.in_backward and world * B <= 64 and B <= 16 and N * F >= 4
-        shape_grads, box_grads, ghids = [None] * 4, [None] * 4, [None] * 4
-
-        def anchor_bwd_group(seqs, xs, sx_m, K, g_list, c0, c1, hid_cat=None, defer_w1=False):
-            """The four MLPs of an anchor kind at once (they are equal in shape): every nn.Linear product of the four in ONE launch
-            (shasta_gemm_strided_group_f32), hidden activations / their gradients / the pre-|.| outputs side by side in (B, 4 H) and
-            (B, 4 out) matrices so that one abs and one column-sum launch serve all four.  Returns (grads per MLP, ghid blocks, ghid)."""
-            n = len(seqs)
-            w1s, b1s = [q[0].weight.detach() for q in seqs], [q[0].bias.detach() for q in seqs]
-            w2s, b2s = [q[2].weight.detach() for q in seqs], [q[2].bias.detach() for q in seqs]
-            H, nout = w1s[0].shape[0], w2s[0].shape[0]
-            blocks = lambda t, w: [t[:, i * w:(i + 1) * w] for i in range(n)]  # noqa: E731
-            if hid_cat is None:
-                hid_cat = torch.empty(B, n * H, device=dev)
-                _gemm_group(lib, xs, (sx_m, 1), w1s, (K, 1), B, H, K, blocks(hid_cat, H), ldc=n * H, biases=b1s, act=1, ws=ws)
-            hids = blocks(hid_cat, H)
-            pre = torch.empty(B, n * nout, device=dev)
-            _gemm_group(lib, hids, (n * H, 1), w2s, (H, 1), B, nout, H, blocks(pre, nout), ldc=n * nout, biases=b2s, ws=ws)
-            g_cat = torch.cat(g_list, dim=1)
-            gpre = torch.empty_like(pre)
-            hip.check(lib.shasta_abs_f32(hip.ptr(pre), hip.ptr(g_cat), hip.ptr(gpre), B * n * nout, nout, c0, c1, 1, st()), "shasta_abs_f32")
-            gb2 = torch.empty(n * nout, device=dev)
-            _colsum(lib, gpre, n * nout, B, n * nout, gb2, ws)
-            gpres = blocks(gpre, nout)
-            gW2 = torch.empty(n, nout, H, device=dev)
-            _gemm_group(lib, gpres, (1, n * nout), hids, (1, n * H), nout, H, B, [gW2[i] for i in range(n)])
-            ghid = torch.empty(B, n * H, device=dev)
-            gh = blocks(ghid, H)
-            _gemm_group(lib, gpres, (n * nout, 1), w2s, (1, H), B, H, nout, gh, ldc=n * H, masks=hids, ldmask=n * H)
-            gb1 = torch.empty(n * H, device=dev)
-            _colsum(lib, ghid, n * H, B, n * H, gb1, ws)
-            gW1s = [None] * n
-            if not defer_w1:
-                gW1s = [torch.empty_like(w) for w in w1s]
-                if B <= 16 and K % 4 == 0 and sx_m % 4 == 0:  # rank-B updates: the streaming kernel, one pass over each output
-                    for i in range(n):
-                        _outer(lib, gh[i], n * H, xs[i], sx_m, B, H, K, gW1s[i])
-                else:
-                    _gemm_group(lib, gh, (1, n * H), xs, (1, sx_m), H, K, B, gW1s)
-            return [(gW1s[i], gb1[i * H:(i + 1) * H], gW2[i], gb2[i * nout:(i + 1) * nout]) for i in range(n)], gh, ghid
-
-        # aug_shape[i]: input = rows < N of feat (i<2) / prev_feat (i>=2); output row N + (i&1) of prev_feat (i<2) / feat (i>=2)
-        Hs_ = N * F // 64
-        ghid_cat = None
-        shape_x = [S["feat"], S["feat"], S["prev_feat"], S["prev_feat"]]
-        shape_gout = [(dprev_feat if i < 2 else dfeat)[:, N + (i & 1), :] for i in range(4)]
-        if Hs_ > 0:
-            grads, ghids, ghid_cat = anchor_bwd_group([model.aug_shape[i] for i in range(4)], shape_x, T * F, N * F, shape_gout, 0, F,
-                                                      hid_cat=S["shape_hidden"], defer_w1=exchange or lowrank)
-            shape_grads = list(grads)
-        else:
-            for i in range(4):
-                shape_grads[i], ghids[i], _ = anchor_bwd(model.aug_shape[i], shape_x[i], T * F, N * F, shape_gout[i].contiguous(), 0, F, hid=None,
-                                                         defer_w1=exchange or lowrank)
-        # dx = ghid W1 into the rows < N of the input table's gradient feeds the gather's backward only: skipped for a map whose gradient
-        # nobody asked for (features from a frozen pipeline; autograd's needs_input_grad), with the gather's backward itself
-        need_dx = [bool(ctx.needs_input_grad[1])] * 2 + [bool(ctx.needs_input_grad[2])] * 2
-        if ghids[0] is not None and not in_bwd and any(need_dx):  # dx = ghid W1 accumulated into the rows < N of the INPUT table's gradient
-            w1s = [model.aug_shape[i][0].weight.detach() for i in range(4)]
-            gins = [dfeat, dfeat, dprev_feat, dprev_feat]
-            if B <= 16 and (N * F) % 4 == 0:  # small batch: stream the 1 GB matrix once (csrc/train.hip)
-                for i in (j for j in range(4) if need_dx[j]):
-                    nb = lib.shasta_smallm_nn_workspace_bytes(B, Hs_, N * F)
-                    sws = torch.empty((nb + 3) // 4, device=dev)
-                    hip.check(lib.shasta_smallm_nn_f32(hip.ptr_view(ghids[i]), ghids[i].stride(0), hip.ptr(w1s[i]), B, Hs_, N * F, hip.ptr(gins[i]),
-                                                       T * F, 1, hip.ptr(sws), nb, st()), "shasta_smallm_nn_f32")
-            else:  # two MLPs add into each table: one launch for the first of each pair, one for the second
-                for pair in ((0, 2), (1, 3)):
-                    pair = [i for i in pair if need_dx[i]]
-                    if pair:
-                        _gemm_group(lib, [ghids[i] for i in pair], (ghids[0].stride(0), 1), [w1s[i] for i in pair], (1, N * F), B, N * F, Hs_,
-                                    [gins[i] for i in pair], ldc=T * F, accum=True)
-        # aug_dets[i]: input = boxes[:, :, :7] before back-projection (det for i<2, prev for i>=2), output anchor box row
-        xb_det, xb_prev = S["det_pre"][:, :, :7].contiguous(), S["prev"][:, :, :7].contiguous()
-        box_x = [xb_det, xb_det, xb_prev, xb_prev]
-        box_gout = [(dprev_tab if i < 2 else ddet_tab)[:, N + (i & 1), :7] for i in range(4)]
-        if 7 * N // 32 > 0:
-            box_grads, _, _ = anchor_bwd_group([model.aug_dets[i] for i in range(4)], box_x, 7 * N, 7 * N, box_gout, 3, 6)
-        else:
-            for i in range(4):
-                box_grads[i], _, _ = anchor_bwd(model.aug_dets[i], box_x[i], 7 * N, 7 * N, box_gout[i].contiguous(), 3, 6)
-
-        if exchange and ghids[0] is not None:
-            Hs_, K = N * F // 64, N * F
-            gh_all = _all_gather_rows(ghid_cat if ghid_cat is not None else torch.cat(ghids, dim=1), world, group)             # (world*B, 4H)
-            xs = [_all_gather_rows(S[k][:, :N, :].reshape(B, K), world, group) for k in ("feat", "prev_feat")]  # (world*B, K)
-            hip.check(lib.shasta_scale_f32(hip.ptr(gh_all), gh_all.numel(), 1.0 / world, st()), "shasta_scale_f32")
-            for i in range(4):
-                w1p = model.aug_shape[i][0].weight
-                if lowrank:  # (the parameter's .grad stays None; allreduce_gradients skips it)
-                    w1p._shasta_grad_factors = (gh_all[:, i * Hs_:], 4 * Hs_, xs[0 if i < 2 else 1], K, world * B)
-                    continue
-                gW1 = torch.empty_like(w1p)
-                _outer(lib, gh_all[:, i * Hs_:], 4 * Hs_, xs[0 if i < 2 else 1], K, world * B, Hs_, K, gW1)
-                g = shape_grads[i]
-                shape_grads[i] = (gW1, g[1], g[2], g[3])
-                w1p._shasta_grad_is_global = True  # allreduce_gradients must not reduce it again
-        elif lowrank and ghids[0] is not None:
-            for i in range(4):  # one rank: the local factors as they are (the input rows lie T * F apart in the feature table)
-                model.aug_shape[i][0].weight._shasta_grad_factors = (ghids[i], ghids[i].stride(0), S["feat"] if i < 2 else S["prev_feat"], T * F, B)
-
-        if in_bwd and ghids[0] is not None:
-            for i in (j for j in range(4) if need_dx[j]):  # (a matrix whose dx nobody needs keeps its factors for step())
-                w1p = model.aug_shape[i][0].weight
-                gin = dfeat if i < 2 else dprev_feat
-                stepper.step_in_backward(w1p, w1p.__dict__.pop("_shasta_grad_factors"), ghids[i], ghids[i].stride(0), B, gin, T * F)
-
-        # ---- gather (shasta.py:231-238) -> gradient of the two NHWC maps ----
-        def gather_bwd(gtab, boxes):
-            Bb, H_, W_, Cc = S["bev_shape"]
-            dbev = torch.zeros(Bb, H_, W_, Cc, device=dev)
-            x0, y0, vx, vy, stv = model.bev_extractor._geom()
-            hip.check(lib.shasta_bev_gather_bwd_f32(hip.ptr(gtab), B, H_, W_, Cc, hip.ptr(boxes), N, boxes.shape[2], N * boxes.shape[2],
-                                                    model.num_point, x0, y0, vx, vy, stv, F, T * F, hip.ptr(dbev), st()),
-                      "shasta_bev_gather_bwd_f32")
-            return dbev
-
-        dbev = gather_bwd(dfeat, S["det_pre"]) if ctx.needs_input_grad[1] else None
-        dprev_bev = gather_bwd(dprev_feat, S["prev"]) if ctx.needs_input_grad[2] else None
-
-        # ---- gradients in the order of affinity_params(model) ----
-        out = []
-        for i in range(4):
-            out += list(shape_grads[i])
-        for gW, gb in fs_grads:
-            out += [gW, gb]
-        for i in range(4):
-            out += list(box_grads[i])
-        for gW, gb in fd_grads:
-            out += [gW, gb]
-        for gW, gb in rc_grads:
-            out += [gW, gb]
-        for gW, gb in aff_grads:
-            out += [gW, gb]
-        return (None, dbev, dprev_bev, None, None) + tuple(out)
+        """The stages of _Backward in reverse forward order."""
+        c = _Backward(ctx.model, ctx.saved)
+        need_bev, need_prev = bool(ctx.needs_input_grad[1]), bool(ctx.needs_input_grad[2])
+        gm = c.softmaxes(g1, g2)
+        aff_grads, gres = c.aff(gm)
+        fs_grads, rc_grads, fd_grads, gdist, denom = c.pair_mlps(gres)
+        c.hand_residual(gdist, denom)
+        shape_grads, ghids, ghid_cat = c.shape_anchors()
+        box_grads = c.box_anchors()
+        shape_grads = c.hand_over(shape_grads, ghids, ghid_cat, need_dx=[need_bev] * 2 + [need_prev] * 2)
+        dbev = c.gather(c.dfeat, c.S["det_pre"]) if need_bev else None
+        dprev_bev = c.gather(c.dprev_feat, c.S["prev"]) if need_prev else None
+        by_module = (shape_grads, fs_grads, box_grads, fd_grads, rc_grads, aff_grads)  # the order of affinity_params(model)
+        return (None, dbev, dprev_bev, None, None) + tuple(t for grads in by_module for g in grads for t in g)
 
 
 def first_layer_plan(model, B, K):
@@ -890,7 +879,7 @@ class GraphedTrainStep:
 def allreduce_gradients(params, world_size=None, bucket_bytes=256 << 20, group=None):
     """Data-parallel gradient averaging over torch.distributed (backend "nccl" = RCCL over xGMI on the GPUs, "gloo" in the
     CPU tests).  The four 1 GB aug_shape first-layer gradients were already averaged inside the backward by exchanging their
-    rank-B factors (_AffinityTrainFn.backward) and are skipped.  The rest is packed into flat buckets (few, large
+    rank-B factors (_Backward.hand_over) and are skipped.  The rest is packed into flat buckets (few, large
     collectives: the per-link bound of the point-to-point xGMI topology favours large messages), summed with one all_reduce
     per bucket and divided by the world size, like apex DDP does for the reference (tools/nusc_shasta/train.py:156)."""
     import torch.distributed as dist

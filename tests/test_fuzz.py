@@ -98,7 +98,9 @@ def _grad_cases(n, seed):
     return [(rnd.choice(sizes), rnd.randint(1, 7), rnd.choice([1, 4, 5]), rnd.choice([1, 2, 5, 17]), 4000 + k) for k in range(n)]
 
 
-@pytest.mark.parametrize("N,nf,npnt,B,seed", _grad_cases(int(os.environ.get("SHASTA_FUZZ_GRAD_CASES", 8)), int(os.environ.get("SHASTA_FUZZ_GRAD_SEED", 9))) + [(100, 7, 4, 2, 4100), (130, 3, 5, 3, 4101), (64, 7, 1, 20, 4102)])
+# the fixed tail: three larger tables, then max_obj = 3 (aug_dets hidden width 7N/32 = 0: the anchor is |bias|) and max_obj = 1, which the
+# random draw above reaches only by chance.  (A width other than F = 64 | 256 | 320 cannot be added here: the forward refuses it.)
+@pytest.mark.parametrize("N,nf,npnt,B,seed", _grad_cases(int(os.environ.get("SHASTA_FUZZ_GRAD_CASES", 8)), int(os.environ.get("SHASTA_FUZZ_GRAD_SEED", 9))) + [(100, 7, 4, 2, 4100), (130, 3, 5, 3, 4101), (64, 7, 1, 20, 4102), (3, 7, 4, 2, 4103), (1, 5, 5, 2, 4106)])
 def test_backward_random_configs_vs_oracle_autograd(N, nf, npnt, B, seed):
     from shasta_amd import training
     dev = torch.device("cuda:0")
