@@ -387,9 +387,11 @@ class Shasta(BaseTrack):
         """shasta.py:223-228: relu(bn(conv3x3(map))) -> NHWC for the current (and, in the same launch, the previous) neck
         output, by the hand-written implicit-GEMM kernels: csrc/shared_conv_f16.hip (arithmetic "f16x2" / "f16grid": fp32 products
         from two fp16 pieces per operand; maps up to 187 columns wide) or csrc/shared_conv.hip (strict f32 MFMA: "f32", "pieces",
-        wider maps).  Eval-mode BatchNorm (running
-        statistics) only: in train() mode the module's own nn.Sequential is used so that batch statistics behave like
-        the reference.  Returns one tensor, or a pair when prev_bev_map is given.  bound: max |x| of the maps as their producer knows
+        wider maps) with the eval-mode BatchNorm (running statistics) folded in.  In train() mode, or when a parameter or a map needs a
+        gradient: batch statistics and the backward for the four shared_conv parameters by the hand-written train-mode path
+        (shared_conv_train.py / csrc/shared_conv_train.hip) for a pair of maps that need no gradient themselves, up to 255 columns wide;
+        the module's own nn.Sequential otherwise (a single map, a map that requires grad, an eval-mode BatchNorm under autograd,
+        hand_written_train_conv = False).  Returns one tensor, or a pair when prev_bev_map is given.  bound: max |x| of the maps as their producer knows
         it (fp16 form only; SharedConvBank.__call__): the pass over the maps that finds it is skipped."""
         conv, bn = self.shared_conv[0], self.shared_conv[1]
         maps = [t for t in (bev_map, prev_bev_map) if t is not None]

@@ -61,7 +61,11 @@ def _case(B, cin, H, W, seed, sparse=False, offset=0.0):
 
 
 @pytest.mark.parametrize("B,cin,H,W,arith", [(2, 512, 180, 180, "f16x2"), (1, 64, 180, 180, "f16x2"), (3, 40, 33, 47, "f16x2"), (2, 8, 24, 24, "f16x2"),
-                                            (1, 16, 12, 200, "f16x2"), (2, 32, 50, 187, "f32"), (1, 48, 7, 5, "f16x2")])
+                                            (1, 16, 12, 200, "f16x2"), (2, 32, 50, 187, "f32"), (1, 48, 7, 5, "f16x2"),
+                                            # the weight gradient's other width classes through the module's glue (img0, edy[i], xmax from
+                                            # the forward's workspace); the kernels alone: tests/test_conv_train_kernels.py
+                                            (1, 8, 9, 100, "f16x2"), (2, 33, 17, 127, "f16x2"), (1, 40, 15, 64, "f16x2"), (1, 16, 5, 63, "f16x2"),
+                                            (1, 16, 3, 255, "f16x2"), (1, 16, 3, 191, "f32")])
 def test_train_mode_shared_conv_against_float64(B, cin, H, W, arith):
     dev = _dev()
     model = _model(cin)
