@@ -9,14 +9,13 @@
 // output row [pt0 C | pt1 C | ...] is written directly in the packed (N, num_point*C) order the
 // reference builds with a cat of sections (bird_eye_view.py:35-37).
 // HBM-bound: 4*C*4 B read + C*4 B written per point.
+#include "bev_gather_point.hpp"
 #include "stages.hpp"
 
 namespace shasta {
 
-// Arithmetic notes (parity): every product/sum below is a separately rounded fp32 op
-// (__fmul_rn/__fadd_rn/__fsub_rn, never contracted) because the reference evaluates them as
-// separate ATen ops; the metric->pixel map keeps the reference's two successive divisions
-// (bird_eye_view.py:19-20) -- a fused reciprocal changes floor() for ~1e-6 of coordinates.
+// Arithmetic notes (parity): where a point falls and its four weights: bev_gather_point.hpp; the four weighted terms below are
+// separately rounded fp32 ops in the reference's order for the same reason.
 // ABSMAX: additionally the largest magnitude written per batch item (bit pattern of a non-negative float, atomicMax: order
 // independent) into the ABSMAX_SLOTS x 128-byte lines absmax[b][slot][0] - the range exponent of the fp16 form of the aug_shape
 // weight stream (anchor_split.hip), which otherwise costs a pass of its own over the tables (row_max_kernel: 0.12 ms at 512
@@ -46,55 +45,10 @@ __global__ __launch_bounds__(256) void bev_gather_kernel(
     const int n = (wave / num_point) % N;
     const int b = wave / (num_point * N);
 
-    const float* box = boxes + (size_t)b * box_batch_stride + (size_t)n * box_stride;
-    const float cx = box[0], cy = box[1];
-    float px = cx, py = cy;
-    // point type: num_point==5 -> [centre, front, back, left, right]; 4 -> no centre; 1 -> centre
-    const int edge = (num_point == 5) ? pt - 1 : (num_point == 4 ? pt : -1);
-    if (edge >= 0) {
-        const float w = box[3], l = box[4], yaw = box[6];
-        const float s = sinf(yaw), c = cosf(yaw);
-        // unit corners (clockwise from the minimum point): (-.5,-.5) (-.5,.5) (.5,.5) (.5,-.5)
-        // edge mid-points: front=(c0+c1)/2, back=(c2+c3)/2, left=(c0+c3)/2, right=(c1+c2)/2
-        const int ia = (edge == 0) ? 0 : (edge == 1) ? 2 : (edge == 2) ? 0 : 1;
-        const int ib = (edge == 0) ? 1 : (edge == 1) ? 3 : (edge == 2) ? 3 : 2;
-        float qx[2], qy[2];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int ci = k ? ib : ia;
-            const float ux = (ci < 2) ? -0.5f : 0.5f;
-            const float uy = (ci == 1 || ci == 2) ? 0.5f : -0.5f;
-            const float dx = __fmul_rn(w, ux), dy = __fmul_rn(l, uy);
-            // rotation_2d: x' = x*cos + y*sin ; y' = -x*sin + y*cos   (box_torch_ops.py:145-158)
-            const float rx = __fadd_rn(__fmul_rn(dx, c), __fmul_rn(dy, s));
-            const float ry = __fadd_rn(__fmul_rn(-dx, s), __fmul_rn(dy, c));
-            qx[k] = __fadd_rn(rx, cx);
-            qy[k] = __fadd_rn(ry, cy);
-        }
-        px = __fdiv_rn(__fadd_rn(qx[0], qx[1]), 2.0f);
-        py = __fdiv_rn(__fadd_rn(qy[0], qy[1]), 2.0f);
-    }
-    const float x = __fdiv_rn(__fdiv_rn(__fsub_rn(px, pc_x0), vs_x), out_stride_px);
-    const float y = __fdiv_rn(__fdiv_rn(__fsub_rn(py, pc_y0), vs_y), out_stride_px);
-    // floor -> int with clamping done in float first so that wild coordinates (inf/NaN/1e30)
-    // cannot overflow the conversion; the reference clamps the int64 indices.
-    const float fx = floorf(x), fy = floorf(y);
-    auto clampi = [](float f, int hi) -> int {
-        if (!(f > -2.0f)) return 0 - 1;  // also NaN -> behaves like far-left (weights become NaN anyway)
-        if (f > (float)(hi + 1)) return hi + 1;
-        return (int)f;
-    };
-    int x0 = clampi(fx, W), y0 = clampi(fy, H);
-    int x1 = x0 + 1, y1 = y0 + 1;
-    x0 = min(max(x0, 0), W - 1);
-    x1 = min(max(x1, 0), W - 1);
-    y0 = min(max(y0, 0), H - 1);
-    y1 = min(max(y1, 0), H - 1);
-    const float fx0 = (float)x0, fx1 = (float)x1, fy0 = (float)y0, fy1 = (float)y1;
-    const float wa = __fmul_rn(__fsub_rn(fx1, x), __fsub_rn(fy1, y));
-    const float wb = __fmul_rn(__fsub_rn(fx1, x), __fsub_rn(y, fy0));
-    const float wc = __fmul_rn(__fsub_rn(x, fx0), __fsub_rn(fy1, y));
-    const float wd = __fmul_rn(__fsub_rn(x, fx0), __fsub_rn(y, fy0));
+    const GatherPoint g = bev_gather_point(boxes + (size_t)b * box_batch_stride + (size_t)n * box_stride, num_point, pt, pc_x0, pc_y0, vs_x, vs_y,
+                                           out_stride_px, H, W);
+    const int x0 = g.x0, x1 = g.x1, y0 = g.y0, y1 = g.y1;
+    const float wa = g.w[0], wb = g.w[1], wc = g.w[2], wd = g.w[3];
 
     const float* im = bev + (size_t)b * H * W * C;
     const float* Ia = im + ((size_t)y0 * W + x0) * C;

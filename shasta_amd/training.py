@@ -7,8 +7,8 @@ forward order - softmaxes, aff, the three pair MLPs with the combine, the hand-d
 aug_dets anchors, the hand-over of the aug_shape first-layer gradients, the gather - and each stage is a method of `_Backward`,
 which carries the sizes, the saved tensors and the four gradient tables.  The stages recompute the activations they need and
 back-propagate with hand-written HIP kernels only: every nn.Linear through the strided matrix-core GEMM (dX = dY W,
-dW = dY^T X, fixed order split-K), everything else through csrc/train.hip and csrc/pair_bwd.hip.  No torch autograd op runs
-inside the Function; torch is used for buffer allocation.  Gradients flow to every parameter of rows 6-16 and to the NHWC BEV
+dW = dY^T X, fixed order split-K), everything else through csrc/backward_aux.hip, csrc/bev_gather_bwd.hip and csrc/pair_bwd.hip.
+No torch autograd op runs inside the Function; torch is used for buffer allocation.  Gradients flow to every parameter of rows 6-16 and to the NHWC BEV
 maps (so `shared_conv`, which stays a torch module in train() mode with batch statistics like the reference, trains through
 ordinary autograd).
 The first layer of each pair MLP is factorised over the table rows in both directions (`_PairMlp`: forward UP[t] + UC[d],
@@ -365,7 +365,7 @@ class _Backward:
         # dx = ghid W1 into the rows < N of the input table's gradient feeds the gather's backward only: skipped for a map whose gradient
         # nobody asked for (features from a frozen pipeline; autograd's needs_input_grad), with the gather's backward itself
         if not in_bwd and any(need_dx):
-            if B <= 16 and K % 4 == 0:  # small batch: stream the 1 GB matrix once (csrc/train.hip)
+            if B <= 16 and K % 4 == 0:  # small batch: stream the 1 GB matrix once (csrc/adam.hip)
                 for i in (j for j in range(4) if need_dx[j]):
                     nb = lib.shasta_smallm_nn_workspace_bytes(B, Hs_, K)
                     sws = torch.empty((nb + 3) // 4, device=dev)
@@ -532,7 +532,7 @@ def affinity_train(model, bev_nhwc, prev_bev_nhwc, det_boxes, prev_det_boxes):
 
 
 class _AffinityLossFn(torch.autograd.Function):
-    """The loss below in two launches and its gradient in one (csrc/train.hip) instead of ~25 elementwise / reduction launches."""
+    """The loss below in two launches and its gradient in one (csrc/backward_aux.hip) instead of ~25 elementwise / reduction launches."""
 
     @staticmethod
     def forward(ctx, m1, m2, gt):

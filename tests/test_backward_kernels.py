@@ -1,4 +1,4 @@
-"""The kink-free kernels of the backward (csrc/train.hip), one by one through the C ABI, against the same formula in torch float64
+"""The kink-free kernels of the backward (csrc/backward_aux.hip), one by one through the C ABI, against the same formula in torch float64
 with autograd - at table sizes T = N + 2 on and around 16, 32, 64, 128, 256, 512 (the trip lengths of these kernels' loops), two
 batch sizes, the leading dimension training.py passes and a larger one, NaN in every padding column and in every output before the call.
 

@@ -22,7 +22,7 @@ LR, EPS = 3e-3, 1e-8
 # ------------------------------------------------------------------------------------------------------------------ the float64 reference
 def adam64(p, m, v, t, g, lr, betas, eps, wd):
     """One Adam step in float64 from the state after t steps: L2 weight decay added to the gradient, bias corrections 1 - beta^t, no
-    amsgrad (the rule adam_one states in csrc/train.hip).  Returns the state after t + 1 steps."""
+    amsgrad (the rule adam_one states in csrc/adam.hip).  Returns the state after t + 1 steps."""
     b1, b2 = betas
     t = t + 1
     g = g + wd * p

@@ -202,7 +202,7 @@ def test_model_forward_is_differentiable_like_the_reference_module():
     assert float(model.shared_conv[0].weight.grad.abs().sum()) > 0
 
 
-# ---- helper kernels of csrc/train.hip, one by one, against torch ---------------------------------------------------------
+# ---- helper kernels of csrc/backward_aux.hip, one by one, against torch ---------------------------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("M,N", [(1, 1), (5000, 1), (70001, 3), (4097, 40), (300, 64), (20000, 130)])
 def test_colsum(M, N):
