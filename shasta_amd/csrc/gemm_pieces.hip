@@ -8,6 +8,9 @@
 // fragments (8 consecutive k per lane).  Two workgroups per CU (60 KB of LDS each): one cuts while the other multiplies.
 // (A one-workgroup-per-CU form with double-buffered LDS, one barrier per slice and the cut interleaved behind the MFMA chains
 // of the same wave measured 61 us instead of 39.5 us on 64 256 x 128 x 256: the second workgroup hides more than the pipeline.)
+// One problem per launch: the kernel serves the C entry shasta_gemm_nt_pieces_f32 only (tests, tools/time_gemm.py) - inside the
+// forward embed_rows.hip took its place.
+#include "gemm_tile.hpp"
 #include "pieces.hpp"
 
 namespace shasta {
@@ -50,10 +53,7 @@ __device__ __forceinline__ void pieces_store(char* img, int tid, const f32x4 (&r
 }
 
 struct GemmPieces {
-    const float* A[2];
-    const float* W[2];
-    const float* bias[2];
-    float* C[2];
+    GemmNtSet<1> p;
     int lda, ldw, ldc, M, N, K, act;
 };
 
@@ -61,11 +61,10 @@ template <bool VEC>
 __global__ __launch_bounds__(256) void gemm_nt_pieces_kernel(GemmPieces g) {
     __shared__ __attribute__((aligned(16))) char s_a[3 * PIMG];
     __shared__ __attribute__((aligned(16))) char s_w[3 * PIMG];
-    const int z = blockIdx.z;
-    const float* __restrict__ A = z ? g.A[1] : g.A[0];
-    const float* __restrict__ W = z ? g.W[1] : g.W[0];
-    const float* __restrict__ bias = z ? g.bias[1] : g.bias[0];
-    float* __restrict__ C = z ? g.C[1] : g.C[0];
+    const float* __restrict__ A = g.p.A[0];
+    const float* __restrict__ W = g.p.W[0];
+    const float* __restrict__ bias = g.p.bias[0];
+    float* __restrict__ C = g.p.C[0];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wm = wid >> 1, wn = wid & 1;
     const int m0 = blockIdx.y * PM, n0 = blockIdx.x * PN;
@@ -120,26 +119,17 @@ __global__ __launch_bounds__(256) void gemm_nt_pieces_kernel(GemmPieces g) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = m0 + wm * 64 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (row < g.M) {
-                    float v = acc[i][j][r] + bv;
-                    if (g.act == 1) v = relu_nan(v);
-                    else if (g.act == 2) v = fabsf(v);
-                    C[(size_t)row * g.ldc + col] = v;
-                }
+                if (row < g.M) C[(size_t)row * g.ldc + col] = gemm_act(acc[i][j][r] + bv, g.act);
             }
     }
 }
 
-// One problem (A1 == nullptr) or two independent problems of the same shape in one launch.
-static int launch_gemm_nt_pieces(const float* A0, const float* W0, const float* bias0, float* C0, const float* A1, const float* W1,
-                                 const float* bias1, float* C1, int lda, int ldw, int ldc, int M, int N, int K, int act, hipStream_t st) {
+static int launch_gemm_nt_pieces(const float* A, const float* W, const float* bias, float* C, int lda, int ldw, int ldc, int M, int N, int K,
+                                 int act, hipStream_t st) {
     if (M == 0 || N == 0) return SHASTA_OK;
-    GemmPieces g{{A0, A1}, {W0, W1}, {bias0, bias1}, {C0, C1}, lda, ldw, ldc, M, N, K, act};
-    uintptr_t al = (uintptr_t)A0 | (uintptr_t)W0;
-    if (A1) al |= (uintptr_t)A1 | (uintptr_t)W1;
-    const bool vec = (lda % 4 == 0) && (ldw % 4 == 0) && (al % 16 == 0);
-    dim3 grid(cdiv(N, PN), cdiv(M, PM), A1 ? 2 : 1);
-    if (vec) hipLaunchKernelGGL(gemm_nt_pieces_kernel<true>, grid, dim3(256), 0, st, g);
+    GemmPieces g{{{A}, {W}, {bias}, {C}}, lda, ldw, ldc, M, N, K, act};
+    dim3 grid(cdiv(N, PN), cdiv(M, PM));
+    if (gemm_vec_ok(lda, ldw, A, W)) hipLaunchKernelGGL(gemm_nt_pieces_kernel<true>, grid, dim3(256), 0, st, g);
     else hipLaunchKernelGGL(gemm_nt_pieces_kernel<false>, grid, dim3(256), 0, st, g);
     return check_launch("gemm_nt_pieces");
 }
@@ -152,5 +142,5 @@ extern "C" int shasta_gemm_nt_pieces_f32(const float* A, int lda, const float* W
     SHASTA_REQUIRE(A && W && C, "gemm_nt_pieces: null pointer");
     SHASTA_REQUIRE(M >= 0 && N >= 0 && K > 0 && lda >= K && ldw >= K && ldc >= N, "gemm_nt_pieces: bad size");
     SHASTA_REQUIRE(act >= 0 && act <= 2, "gemm_nt_pieces: bad activation");
-    return launch_gemm_nt_pieces(A, W, bias, C, nullptr, nullptr, nullptr, nullptr, lda, ldw, ldc, M, N, K, act, as_stream(stream));
+    return launch_gemm_nt_pieces(A, W, bias, C, lda, ldw, ldc, M, N, K, act, as_stream(stream));
 }

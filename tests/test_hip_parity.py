@@ -727,6 +727,57 @@ def test_precut_weight_stream_is_bit_identical(N, B):
     assert all(torch.equal(a, b) for a, b in zip(plain2, pre2)) and not torch.equal(pre2[3], pre[3])
 
 
+def test_anchor_direct_gemm_at_256_frame_pairs():
+    """gemm_nt_f32_direct_quad_kernel (gemm_f32.hip) at the smallest shape that reaches it from both of its callers in anchor.hip: from
+    256 frame-pairs the second aug_shape layers (K = H = N F / 64 = 512 at max_obj 128, F = 256) and the first aug_dets layers
+    (K = 7 N = 896, a multiple of 4) are four skinny long-K products in one launch.  257 items: row tiles 0 - 7 are full, tile 8 holds one
+    row (the kernel's row clamp and its store guard).  Items 0, 100 and 256 against the CPU oracle on those items alone, at the
+    intermediates tolerance of tests/helpers.py (the oracle itself measures 1.4e-6 against float64 here, 0.29 of that bound); every item
+    against the same model on four batches of 64 / 65, which take the small-batch kernels, at the bar of "same item, other summation
+    order" of the test above.  Both weight-stream arithmetics: they differ in the first-layer kernel that feeds the hidden rows."""
+    import shasta_amd
+    from tests.helpers import PIN_TOL, _close
+    dev = _dev()
+    N, B = 128, 257
+    torch.manual_seed(N)
+    m = shasta_amd.build_simp_track(dict(type="Shasta", reader=None, backbone=None, neck=None,
+                                         bev_extractor=dict(type="BEVFeatureExtractor", pc_start=[-54, -54], voxel_size=[0.075, 0.075],
+                                                            out_stride=30), max_obj=N, num_feats=7, num_point=4, in_channels=8)).eval()
+    w = {k: v.detach().clone() for k, v in m.state_dict().items()}
+    g = torch.Generator().manual_seed(B)
+    bev = torch.relu(torch.randn(B, 48, 48, 64, generator=g))
+    det, prev = O.synth_boxes(g, B, N), O.synth_boxes(g, B, N)
+    probe = [0, 100, 256]  # first tile, an inner tile, the ragged tile
+    det_ref = det[probe].clone()
+    _, _, im = O.forward_from_bev(w, bev[probe], bev[probe], det_ref, prev[probe].clone(), 7, 4, out_stride=30, return_intermediates=True)
+    ref = dict(feature=torch.cat([im["dead_trk_geom"], im["fn_geom"]], 1), prev_feature=torch.cat([im["newborn_geom"], im["fp_geom"]], 1),
+               det_tab=torch.cat([im["dead_trk"], im["fn"]], 1), prev_tab=torch.cat([im["newborn"], im["fp"]], 1), xy=det_ref[:, :, :2])
+    m = m.to(dev)
+    m.keep_intermediates = True
+    bev, det, prev = bev.to(dev), det.to(dev), prev.to(dev)
+
+    def run(lo, hi):
+        d = det[lo:hi].clone()
+        with torch.no_grad():
+            m.affinity_from_bev(bev[lo:hi], bev[lo:hi], d, prev[lo:hi])
+        im = m.last_intermediates
+        return dict(feature=im["feature"][:, N:].clone(), prev_feature=im["prev_feature"][:, N:].clone(),
+                    det_tab=im["det_tab"][:, N:, :7].clone(), prev_tab=im["prev_tab"][:, N:, :7].clone(), xy=d[:, :, :2])
+
+    for mode in ("f16x2", "f32"):
+        m.arithmetic = mode
+        big = run(0, B)
+        parts = [run(lo, hi) for lo, hi in ((0, 64), (64, 128), (128, 192), (192, 257))]
+        for k, tol in (("feature", PIN_TOL["geom"]), ("prev_feature", PIN_TOL["geom"]), ("det_tab", PIN_TOL["anchors"]),
+                       ("prev_tab", PIN_TOL["anchors"]), ("xy", PIN_TOL["anchors"])):
+            assert torch.isfinite(big[k]).all()
+            worst = _close("%s %s, items 0 / 100 / 256 against the oracle" % (mode, k), big[k][probe].cpu().numpy(), ref[k].numpy(), tol)
+            small = torch.cat([p[k] for p in parts])
+            diff, scale = float((small - big[k]).abs().max()), float(big[k].abs().max())
+            print("%s %s: %.3f of the oracle bound, |small batches - 257| = %.3e (max|257| = %.3e)" % (mode, k, worst, diff, scale))
+            assert diff <= 2e-5 * scale, (mode, k, diff, scale)
+
+
 @pytest.mark.parametrize("npnt,nf", [(4, 7), (5, 3)])
 @pytest.mark.parametrize("B", [3, 70])
 def test_non_finite_inputs_stay_non_finite(B, npnt, nf):
