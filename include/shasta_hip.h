@@ -171,6 +171,37 @@ int shasta_shared_conv_multi_f32(const float* x, const float* x_prev, int B, int
                                  shasta_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The RPN neck, one layer per call (csrc/neck.hip): conv or transposed conv (no bias) + BatchNorm2d (eval) + ReLU, NCHW in and out
+ * replaces det3d/models/necks/rpn.py:125-163 (`_make_layer` blocks, the deblocks and the `torch.cat` of `forward`) layer by layer.
+ * Strict fp32: v_mfma_f32_32x32x2_f32 products and accumulation, y = relu(conv(x) * alpha + beta'), alpha = gamma / sqrt(var + eps),
+ * beta' = beta - mean * alpha.  No atomics: the same bits on every run.
+ *
+ *  kind    SHASTA_NECK_C3S1  Conv2d(3, padding 1) - also ZeroPad2d(1) + Conv2d(3, stride 1) -, weight (Cout, Cin, 3, 3), out H x W
+ *          SHASTA_NECK_C3S2  ZeroPad2d(1) + Conv2d(3, stride 2), weight (Cout, Cin, 3, 3), out H/2 x W/2; H and W even
+ *          SHASTA_NECK_C1    ConvTranspose2d(kernel 1, stride 1), weight (Cin, Cout, 1, 1), out H x W
+ *          SHASTA_NECK_D2    ConvTranspose2d(kernel 2, stride 2), weight (Cin, Cout, 2, 2), out 2H x 2W
+ *  shasta_neck_layer_supported : 1 when the kernels serve the layer: Cin % 8 == 0, Cout % 32 == 0, H, W >= 1 (even for C3S2), one
+ *          image below 2^31 elements.  Every other layer is refused with SHASTA_E_UNSUPPORTED before any launch, and so is a call
+ *          whose B x ceil(Cout / 64) (x 4 for D2) exceeds 65535 (the grid limit: split the batch).
+ *  packed : shasta_neck_layer_packed_bytes(kind, Cin, Cout) bytes (0 for an unsupported layer), 16-byte aligned, written by
+ *          shasta_neck_layer_pack_f32 from the layer's weight and the four BatchNorm tensors; re-pack when one of them changes
+ *  x      : (B, Cin, H, W) fp32 NCHW
+ *  out    : (B, out_channels_total, OH, OW) fp32 NCHW; the layer writes channels [out_channel_offset, out_channel_offset + Cout) and
+ *          touches no other (the two deblocks write the halves of the concatenated neck output in place: no pass for torch.cat)
+ * ------------------------------------------------------------------------------------------ */
+#define SHASTA_NECK_C3S1 0
+#define SHASTA_NECK_C3S2 1
+#define SHASTA_NECK_C1 2
+#define SHASTA_NECK_D2 3
+int shasta_neck_layer_supported(int kind, int Cin, int Cout, int H, int W);
+size_t shasta_neck_layer_packed_bytes(int kind, int Cin, int Cout);
+int shasta_neck_layer_pack_f32(const float* weight, const float* bn_weight, const float* bn_bias, const float* bn_mean,
+                               const float* bn_var, float bn_eps, int kind, int Cin, int Cout, void* packed, size_t packed_bytes,
+                               shasta_stream_t stream);
+int shasta_neck_layer_f32(const float* x, int B, int Cin, int H, int W, const void* packed, size_t packed_bytes, int kind, int Cout,
+                          float* out, int out_channels_total, int out_channel_offset, shasta_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * K0 in train() mode (csrc/shared_conv_train.hip): what autograd does for `self.shared_conv(bev_map)` when the reference trains it -
  * tools/nusc_shasta/train.py:183-191 freezes children 1, 2 (backbone, neck) only and keeps every BatchNorm in train mode; the
  * optimizer (:143-147) holds shared_conv.0.{weight,bias} and shared_conv.1.{weight,bias}.  The neck is frozen: no input gradient.

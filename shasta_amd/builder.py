@@ -1,8 +1,9 @@
 """`build_*` entry points of det3d/models/builder.py:20-75 for the registries this path uses.
 
-A None config builds nothing (returns None): the spconv backbone and the RPN neck are CenterPoint upstream code outside
-this package; a user who has them registers their classes in BACKBONES / NECKS and the
-Shasta module calls them exactly like the reference.  A list of configs becomes an nn.Sequential, like the reference."""
+A None config builds nothing (returns None).  NECKS holds `RPN` (shasta_amd/neck.py: the reference's neck on the kernels of
+csrc/neck.hip).  The spconv backbone is CenterPoint upstream code outside this package; a user
+who has it registers the class in BACKBONES and the Shasta module calls it exactly like the reference.  A list of configs
+becomes an nn.Sequential, like the reference."""
 from torch import nn
 
 from . import registry as R

@@ -68,6 +68,10 @@ SYMBOLS = {
     "shasta_shared_conv_multi_workspace_bytes_for": (_Z, [_I, _I, _I, _I, _I, _I]),
     "shasta_shared_conv_multi_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _Z, _I, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _P, _Z, _P]),
     "shasta_shared_conv_multi_bounded_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _Z, _I, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _P, _Z, _F, _P]),
+    "shasta_neck_layer_supported": (_I, [_I, _I, _I, _I, _I]),
+    "shasta_neck_layer_packed_bytes": (_Z, [_I, _I, _I]),
+    "shasta_neck_layer_pack_f32": (_I, [_P, _P, _P, _P, _P, _F, _I, _I, _I, _P, _Z, _P]),
+    "shasta_neck_layer_f32": (_I, [_P, _I, _I, _I, _I, _P, _Z, _I, _I, _P, _I, _I, _P]),
     "shasta_conv_train_supported": (_I, [_I, _I, _I]),
     "shasta_shared_conv_pack_raw_f32": (_I, [_P, _P, _I, _P, _Z, _P]),
     "shasta_shared_conv_pack_raw_f16x2": (_I, [_P, _P, _I, _P, _Z, _P]),

@@ -185,9 +185,9 @@ class Shasta(BaseTrack):
             print("no pretrained model at {} ({})".format(pretrained, e))
 
     def extract_feat(self, data):
-        """shasta.py:164-210.  With a backbone/neck registered by the user the call sequence is the reference's.
-        Without them (this package does not ship the spconv backbone or the RPN) the neck outputs are read from
-        `data['bev_map']`, `data['prev_bev_map']` (B, in_channels, H, W)."""
+        """shasta.py:164-210.  With a backbone configured the call sequence is the reference's: reader -> backbone -> neck (the
+        registered `RPN` of shasta_amd/neck.py runs on the kernels of csrc/neck.hip; the spconv backbone is the user's to register).
+        Without a backbone the neck outputs are read from `data['bev_map']`, `data['prev_bev_map']` (B, in_channels, H, W)."""
         if self.backbone is None:
             if "bev_map" not in data or "prev_bev_map" not in data:
                 raise KeyError("Shasta.extract_feat: no backbone configured and example has no 'bev_map'/'prev_bev_map' "

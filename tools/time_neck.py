@@ -1,0 +1,80 @@
+"""Time the RPN neck at the shipped shape (configs/nusc: 256 -> 128 / 256 -> 512 channels, layer_nums [5, 5], 180 x 180 maps) on the
+hand-written kernels (RPN.forward, csrc/neck.hip) and, with the same weights in the same run, through the module's own nn layers
+(RPN.forward_layers: MIOpen).  HIP events after a warm-up; one JSON line.
+
+    python tools/time_neck.py [--batches 1 2 8] [--iters 10] [--hw 180]
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.getcwd())
+import shasta_amd  # noqa: E402
+from shasta_amd import hip, neck  # noqa: E402
+
+SHIPPED = dict(layer_nums=[5, 5], ds_layer_strides=[1, 2], ds_num_filters=[128, 256], us_layer_strides=[1, 2], us_num_filters=[256, 256],
+               num_input_features=256)
+KIND = {neck.C3S1: "C3S1", neck.C3S2: "C3S2", neck.C1: "C1", neck.D2: "D2"}
+
+
+def timed(fn, iters, warmup=3):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def layer_flops(kind, conv, h, w):
+    """FLOP of one layer on one (h, w) input map (2 per multiply-add)."""
+    taps, pix = (9, h * w) if kind == neck.C3S1 else (9, h * w // 4) if kind == neck.C3S2 else (1, h * w) if kind == neck.C1 else (4, h * w)
+    return 2 * conv.in_channels * conv.out_channels * taps * pix
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", type=int, nargs="+", default=[1, 2, 8])
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--hw", type=int, default=180)
+    ap.add_argument("--no-layers", action="store_true", help="skip the per-layer timing")
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    m = shasta_amd.builder.build_neck(dict(type="RPN", **SHIPPED)).eval().to(dev)
+    shapes = m._shapes(a.hw, a.hw)
+    flop = sum(layer_flops(k, conv, s[0], s[1]) for (k, conv, _, _), s in zip(m._plan, shapes))
+    res = dict(tool="time_neck", hw=a.hw, gflop_per_map=round(flop / 1e9, 2), device=torch.cuda.get_device_name(0), batches=[])
+    with torch.no_grad():
+        for B in a.batches:
+            x = torch.relu(torch.randn(B, 256, a.hw, a.hw, device=dev))
+            t_hip = timed(lambda: m(x), a.iters)
+            t_nn = timed(lambda: m.forward_layers(x), a.iters)
+            res["batches"].append(dict(B=B, hip_ms=round(t_hip, 3), hip_tflops=round(B * flop / t_hip / 1e9, 1), miopen_ms=round(t_nn, 3),
+                                       miopen_tflops=round(B * flop / t_nn / 1e9, 1)))
+        if not a.no_layers:  # every layer of the chain on its own, B = 1 (the same launches RPN.forward makes)
+            lib, s = hip.load(), hip.stream_ptr()
+            x = torch.relu(torch.randn(1, 256, a.hw, a.hw, device=dev))
+            m(x)
+            layers = []
+            for (kind, conv, _, _), pk, sh in zip(m._plan, m._packed, shapes):
+                xin = torch.relu(torch.randn(1, conv.in_channels, sh[0], sh[1], device=dev))
+                out = torch.empty(1, conv.out_channels, sh[2], sh[3], device=dev)
+                ms = timed(lambda: hip.check(lib.shasta_neck_layer_f32(hip.ptr(xin), 1, conv.in_channels, sh[0], sh[1], hip.ptr(pk), pk.numel(), kind,
+                                                                       conv.out_channels, hip.ptr(out), conv.out_channels, 0, s), "neck_layer"), a.iters)
+                f = layer_flops(kind, conv, sh[0], sh[1])
+                layers.append(dict(kind=KIND[kind], cin=conv.in_channels, cout=conv.out_channels, hw=sh[0], gflop=round(f / 1e9, 2), ms=round(ms, 4),
+                                   tflops=round(f / ms / 1e9, 1)))
+            res["layers_b1"] = layers
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
