@@ -202,6 +202,59 @@ int shasta_neck_layer_f32(const float* x, int B, int Cin, int H, int W, const vo
                           float* out, int out_channels_total, int out_channel_offset, shasta_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The sparse 3-D backbone, one step per call (csrc/sparse_conv.hip): replaces what det3d/models/backbones/scn.py:98-211
+ * (`SpMiddleResNetFHD`, eval mode) asks of spconv - SubMConv3d, SparseConv3d, BatchNorm1d over the feature rows, the residual add of
+ * `SparseBasicBlock` and `SparseConvTensor.dense()`.  Strict fp32 on the f32 MFMA: per output a fixed-order chain over the taps in
+ * (kz, ky, kx) row-major order, then over the input channels; no float atomics, the same bits on every run and for every row order.
+ *
+ *  coords : (n, 4) int32 rows (batch, z, y, x); a level's grid is (D, H, W), B x D x H x W < 2^31 cells.
+ *           PRECONDITION: the rows of a level are unique and inside the grid (the voxeliser guarantees both).  Every kernel still
+ *           range-checks each coordinate it turns into an address: a row outside the grid is inactive (no site, no neighbour, nothing
+ *           written by the densify).  n = 0 is valid everywhere.
+ *  geometry (kd, kh, kw, sd, sh, sw, pd, ph, pw): kernel 1 or 3, stride 1 or 2, padding 0 or 1 per axis; a submanifold convolution is
+ *           (3,3,3, 1,1,1, 1,1,1) over the level's own rows.  Output grid per axis O = (I + 2p - k) / s + 1.
+ *  index  : shasta_spconv_index_workspace_bytes(B, D, H, W, rows) bytes, 16-byte aligned: a bitmap of the level's grid, prefix counts of
+ *           its set bits and the row of every active cell (0 for a grid that is not served).  Filled by shasta_spconv_index_rows for rows
+ *           in the caller's order, or by shasta_spconv_out_coords for the level a strided convolution produces; read by
+ *           shasta_spconv_neighbors.  The convolutions that share an `indice_key` share one neighbour table.
+ *  shasta_spconv_out_coords : the active sites of the output level (a site is active iff one of its taps meets an active input site
+ *           inside the grid), unique and SORTED by linear index ((b D + z) H + y) W + x, rows [0, min(*n_out, out_capacity)) of
+ *           out_coords; *n_out (a device word) receives the full count.  n_in * ceil(k/s) per axis bounds it.  `index_workspace`
+ *           (of the OUTPUT grid, rows = out_capacity) is left holding that level's index.
+ *  shasta_spconv_neighbors : neighbors[(o, t)] = the input row at o * s - p + t (t = (tz * kh + ty) * kw + tx), -1 where that site is
+ *           outside the grid, inactive or in another batch item; (n_out, K) int32, K = kd kh kw.  (D, H, W) and the index are the
+ *           INPUT level's; n_in its row count.
+ *  packed : shasta_spconv_layer_packed_bytes(Cin, Cout, K) bytes (0 when not served), 16-byte aligned, written by
+ *           shasta_spconv_layer_pack_f32 from the weight in the spconv 2.x layout (Cout, kD, kH, kW, Cin), the optional bias (NULL:
+ *           none) and the four BatchNorm1d tensors: alpha = gamma / sqrt(var + eps), beta' = beta + (bias - mean) * alpha.
+ *  shasta_spconv_layer_f32 : out[o] = relu?( (sum_t W_t x[neighbors[o, t]]) * alpha + beta' + residual[o]? ), rows of Cout floats.
+ *           x: (n_in, Cin) rows, 16-byte aligned when Cin > 8; residual: (n_out, Cout) or NULL; out must not alias x (it may alias
+ *           residual).  Rows >= n_out of out are not written.  A neighbour index outside [0, n_in) counts as absent.
+ *           Served: Cin <= 8 (zero-padded to 8 at pack time), 16, 32, 64, 128; Cout 16, 32, 64, 128; K 1, 3, 9, 27.  Everything else,
+ *           here and in shasta_spconv_supported, is SHASTA_E_UNSUPPORTED before any launch.
+ *  shasta_spconv_dense_f32 : zero-fill and scatter in one call: out (B, C, D, H, W) = (B, C * D, H, W) fp32 NCHW, channel c * D + z;
+ *           exact zeros at inactive sites.
+ * ------------------------------------------------------------------------------------------ */
+int shasta_spconv_supported(int Cin, int Cout, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw);
+size_t shasta_spconv_index_workspace_bytes(int B, int D, int H, int W, int rows);
+int shasta_spconv_index_rows(const int* coords, int n, int B, int D, int H, int W, void* index_workspace, size_t workspace_bytes,
+                             shasta_stream_t stream);
+int shasta_spconv_out_coords(const int* coords, int n_in, int B, int D, int H, int W, int kd, int kh, int kw, int sd, int sh, int sw,
+                             int pd, int ph, int pw, int* out_coords, int out_capacity, int* n_out, void* index_workspace,
+                             size_t workspace_bytes, shasta_stream_t stream);
+int shasta_spconv_neighbors(const int* out_coords, int n_out, int B, int D, int H, int W, int kd, int kh, int kw, int sd, int sh, int sw,
+                            int pd, int ph, int pw, const void* index_workspace, size_t workspace_bytes, int n_in, int* neighbors,
+                            shasta_stream_t stream);
+size_t shasta_spconv_layer_packed_bytes(int Cin, int Cout, int K);
+int shasta_spconv_layer_pack_f32(const float* weight, const float* bias, const float* bn_weight, const float* bn_bias,
+                                 const float* bn_mean, const float* bn_var, float bn_eps, int Cin, int Cout, int K, void* packed,
+                                 size_t packed_bytes, shasta_stream_t stream);
+int shasta_spconv_layer_f32(const float* x, int n_in, int Cin, const int* neighbors, int n_out, int K, const void* packed,
+                            size_t packed_bytes, int Cout, const float* residual, int relu, float* out, shasta_stream_t stream);
+int shasta_spconv_dense_f32(const float* features, const int* coords, int n, int B, int C, int D, int H, int W, float* out,
+                            shasta_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * K0 in train() mode (csrc/shared_conv_train.hip): what autograd does for `self.shared_conv(bev_map)` when the reference trains it -
  * tools/nusc_shasta/train.py:183-191 freezes children 1, 2 (backbone, neck) only and keeps every BatchNorm in train mode; the
  * optimizer (:143-147) holds shared_conv.0.{weight,bias} and shared_conv.1.{weight,bias}.  The neck is frozen: no input gradient.

@@ -2,7 +2,7 @@
 
 Host code mirrors the reference's model/registry API (tools/nusc_shasta call surface); compute is hand-written HIP
 for gfx950 behind the C ABI in include/shasta_hip.h.  See DESIGN.md and INTEGRATION.md."""
-from . import hip  # noqa: F401
+from . import backbone, hip  # noqa: F401  (backbone.SpMiddleResNetFHD is NOT registered at import: backbone.register())
 from .bird_eye_view import BEVFeatureExtractor  # noqa: F401
 from .builder import build_simp_track, build_track  # noqa: F401
 from .neck import RPN  # noqa: F401

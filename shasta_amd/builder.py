@@ -1,9 +1,10 @@
 """`build_*` entry points of det3d/models/builder.py:20-75 for the registries this path uses.
 
 A None config builds nothing (returns None).  NECKS holds `RPN` (shasta_amd/neck.py: the reference's neck on the kernels of
-csrc/neck.hip).  The spconv backbone is CenterPoint upstream code outside this package; a user
-who has it registers the class in BACKBONES and the Shasta module calls it exactly like the reference.  A list of configs
-becomes an nn.Sequential, like the reference."""
+csrc/neck.hip).  BACKBONES is empty at import: the sparse backbone `SpMiddleResNetFHD` (shasta_amd/backbone.py, eval-mode forward on
+csrc/sparse_conv.hip, no spconv) is passed as a class - `backbone=dict(type=shasta_amd.backbone.SpMiddleResNetFHD, ...)` - or
+registered under its name by `shasta_amd.backbone.register()` for the reference's string configs; the Shasta module calls it
+exactly like the reference.  A list of configs becomes an nn.Sequential, like the reference."""
 from torch import nn
 
 from . import registry as R

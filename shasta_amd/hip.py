@@ -72,6 +72,15 @@ SYMBOLS = {
     "shasta_neck_layer_packed_bytes": (_Z, [_I, _I, _I]),
     "shasta_neck_layer_pack_f32": (_I, [_P, _P, _P, _P, _P, _F, _I, _I, _I, _P, _Z, _P]),
     "shasta_neck_layer_f32": (_I, [_P, _I, _I, _I, _I, _P, _Z, _I, _I, _P, _I, _I, _P]),
+    "shasta_spconv_supported": (_I, [_I] * 11),
+    "shasta_spconv_index_workspace_bytes": (_Z, [_I] * 5),
+    "shasta_spconv_index_rows": (_I, [_P, _I, _I, _I, _I, _I, _P, _Z, _P]),
+    "shasta_spconv_out_coords": (_I, [_P] + [_I] * 14 + [_P, _I, _P, _P, _Z, _P]),
+    "shasta_spconv_neighbors": (_I, [_P] + [_I] * 14 + [_P, _Z, _I, _P, _P]),
+    "shasta_spconv_layer_packed_bytes": (_Z, [_I, _I, _I]),
+    "shasta_spconv_layer_pack_f32": (_I, [_P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _P, _Z, _P]),
+    "shasta_spconv_layer_f32": (_I, [_P, _I, _I, _P, _I, _I, _P, _Z, _I, _P, _I, _P, _P]),
+    "shasta_spconv_dense_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "shasta_conv_train_supported": (_I, [_I, _I, _I]),
     "shasta_shared_conv_pack_raw_f32": (_I, [_P, _P, _I, _P, _Z, _P]),
     "shasta_shared_conv_pack_raw_f16x2": (_I, [_P, _P, _I, _P, _Z, _P]),

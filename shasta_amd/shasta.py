@@ -186,7 +186,8 @@ class Shasta(BaseTrack):
 
     def extract_feat(self, data):
         """shasta.py:164-210.  With a backbone configured the call sequence is the reference's: reader -> backbone -> neck (the
-        registered `RPN` of shasta_amd/neck.py runs on the kernels of csrc/neck.hip; the spconv backbone is the user's to register).
+        registered `RPN` of shasta_amd/neck.py runs on the kernels of csrc/neck.hip; the sparse backbone of shasta_amd/backbone.py on those
+        of csrc/sparse_conv.hip - passed as a class or registered by backbone.register()).
         Without a backbone the neck outputs are read from `data['bev_map']`, `data['prev_bev_map']` (B, in_channels, H, W)."""
         if self.backbone is None:
             if "bev_map" not in data or "prev_bev_map" not in data:
