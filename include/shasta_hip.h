@@ -86,6 +86,29 @@ int shasta_voxelize_mean_batch_f32(const float* points, const int* h_offsets, in
                                    int32_t* num_points_per_voxel, float* mean, int32_t* num_voxels, void* workspace,
                                    size_t workspace_bytes, shasta_stream_t stream);
 
+/* Dynamic voxelisation and the mean of ALL points of every voxel, the reference's DynamicVoxelEncoder
+ * (det3d/models/readers/dynamic_voxel_encoder.py:8-17,83-102): no cap on the points of a voxel, none on the voxels.  Clouds back to back
+ * as above ((sum P, ndim) fp32, h_offsets[0..num_clouds] on the HOST, num_clouds <= 32), 3 <= ndim <= 32.
+ *  keep        a point iff lo_j <= p_j <= hi_j on x, y, z in fp32 (both faces inclusive; NaN and infinities drop out)
+ *  coordinate  (int)((p_j - lo_j) / vs_j), fp32 subtraction and true division.  A point on an upper face has coordinate == g_j, one past
+ *              the grid; its voxel IS emitted, as in the reference: the cell space per cloud is (gz+1) x (gy+1) x (gx+1), and
+ *              num_clouds * (gz+1)(gy+1)(gx+1) must stay below 2^31 (16 clouds at 1440 x 1440 x 40 do).
+ *  gx, gy, gz  the reader's `shape` = round((hi - lo) / vs), computed by the caller; refused when trunc((hi - lo) / vs) exceeds it.
+ *  voxels      (capacity, ndim) fp32: the sum of the voxel's points, added one by one in ascending point index, divided by the count -
+ *              bit for bit what scatter_mean gives on the CPU, the same bits on every run (no float atomics)
+ *  coors       (capacity, 4) int32 rows (cloud, z, y, x): per cloud sorted lexicographically by (z, y, x), clouds in order
+ *  num_points  (capacity,) int32 or NULL
+ *  num_voxels  (num_clouds + 1,) int32 ON THE DEVICE: voxels before each cloud, the last word is V (no host read inside the call).
+ *              Rows at or beyond min(V, capacity) are not written; V is the full count even when capacity is smaller.
+ *  workspace   shasta_dynvox_workspace_bytes (0 for a shape that is not served), 16-byte aligned: a bitmap of all clouds' cells with
+ *              its prefix counts, and per-point index lists.
+ * Unserved shapes return SHASTA_E_UNSUPPORTED, a short workspace SHASTA_E_WORKSPACE, both before any launch.  Empty clouds, clouds
+ * wholly out of range and sum P = 0 are valid. */
+size_t shasta_dynvox_workspace_bytes(const int* h_offsets, int num_clouds, int gx, int gy, int gz);
+int shasta_dynvox_mean_f32(const float* points, const int* h_offsets, int num_clouds, int ndim, const float* h_range6,
+                           const float* h_voxel3, int gx, int gy, int gz, float* voxels, int32_t* coors, int32_t* num_points,
+                           int capacity, int32_t* num_voxels, void* workspace, size_t workspace_bytes, shasta_stream_t stream);
+
 /* The reader alone, for callers that already hold voxelised input (det3d/models/readers/voxel_encoder.py:18-28 as called from
  * Shasta.extract_feat, det3d/models/tracker/shasta.py:178-179): out (V, num_features) = sum over the max_points slots of
  * voxels (V, max_points, ndim)[..., :num_features] / num_points.  num_points_f32: (V,) fp32 - example_to_device

@@ -4,7 +4,8 @@ A None config builds nothing (returns None).  NECKS holds `RPN` (shasta_amd/neck
 csrc/neck.hip).  BACKBONES is empty at import: the sparse backbone `SpMiddleResNetFHD` (shasta_amd/backbone.py, eval-mode forward on
 csrc/sparse_conv.hip, no spconv) is passed as a class - `backbone=dict(type=shasta_amd.backbone.SpMiddleResNetFHD, ...)` - or
 registered under its name by `shasta_amd.backbone.register()` for the reference's string configs; the Shasta module calls it
-exactly like the reference.  A list of configs becomes an nn.Sequential, like the reference."""
+exactly like the reference.  BEV holds `SingleStageBEV` and `BEVMap` (shasta_amd/bevmap.py), the stand-alone reader -> backbone -> neck
+module whose weights are `bev_map.pth`.  A list of configs becomes an nn.Sequential, like the reference."""
 from torch import nn
 
 from . import registry as R
@@ -32,3 +33,4 @@ build_neck = _plain(R.NECKS)
 build_second_stage_module = _plain(R.SECOND_STAGE)
 build_simp_track = _with_run_cfgs(R.TRACK)
 build_track = _with_run_cfgs(R.TRACK)
+build_bev = _with_run_cfgs(R.BEV)  # builder.py:66: BEVMap / SingleStageBEV (shasta_amd/bevmap.py)

@@ -61,4 +61,4 @@ def build_from_cfg(cfg, registry, default_args=None):
     return _resolve(cfg["type"], registry)(**kwargs)
 
 
-READERS, BACKBONES, NECKS, TRACK, SECOND_STAGE = (Registry(n) for n in ("reader", "backbone", "neck", "track", "second_stage"))
+READERS, BACKBONES, NECKS, TRACK, SECOND_STAGE, BEV = (Registry(n) for n in ("reader", "backbone", "neck", "track", "second_stage", "bev"))
