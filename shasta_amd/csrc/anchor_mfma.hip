@@ -227,7 +227,7 @@ __global__ __launch_bounds__(256) void anchor_l1_mfma_kernel(AnchorMfmaArgs a) {
                 float* o = a.part + ((size_t)ks * a.B + b) * (4 * a.H) + mlp * a.H;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int row = r0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int row = r0 + mfma32_row(r, h);
                     if (row < a.H) o[row] = acc32[u][r];
                 }
             }

@@ -479,7 +479,7 @@ __global__ __launch_bounds__(256) void anchor_l1_split_kernel(AnchorSplitArgs a)
                 float* o = a.part + ((size_t)ks * a.B + b) * (4 * a.H) + mlp * a.H;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int row = r0 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                    const int row = r0 + mfma32_row(r, fh);
                     if (row < a.H) o[row] = acc[u][r];
                 }
             }
@@ -641,7 +641,7 @@ __global__ __launch_bounds__(512) void anchor_l1_wide_kernel(AnchorSplitArgs a) 
             float* o = a.part + ((size_t)ks * a.B + b) * (4 * a.H) + mlp * a.H;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = r0 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                const int row = r0 + mfma32_row(r, fh);
                 if (row < a.H) o[row] = acc[j][u][r];
             }
         }

@@ -94,4 +94,7 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
+// Row of a 32 x 32 MFMA result D that accumulator register r (0 .. 15) of lane half h = lane >> 5 holds; the column is lane & 31.
+__device__ __forceinline__ int mfma32_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
 }  // namespace shasta

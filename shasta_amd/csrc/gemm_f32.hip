@@ -223,7 +223,7 @@ struct NtTile {
             const float bv = bias ? bias[col] : 0.0f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                const int row = m0 + wm * 32 + mfma32_row(r, lane >> 5);
                 if (row < a_.rows) C[(size_t)row * ldc + col] = gemm_act(acc[r] + bv, act);
             }
         }
@@ -491,7 +491,7 @@ __device__ __forceinline__ void strided_epilogue(const GemmS& g, const f32x16& a
         const float bv = (g.bias && blockIdx.z == 0) ? g.bias[col] : 0.0f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const int row = m0 + wm * 32 + mfma32_row(r, lane >> 5);
             if (row < g.M) {
                 float v = gemm_act(acc[r] + bv, g.act & 3);
                 if (g.mask && !(g.mask[(long)row * g.ldmask + col] > 0.0f)) v = 0.0f;

@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256) void gemm_nt_pieces_kernel(GemmPieces g) {
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = m0 + wm * 64 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                const int row = m0 + wm * 64 + 32 * i + mfma32_row(r, lane >> 5);
                 if (row < g.M) C[(size_t)row * g.ldc + col] = gemm_act(acc[i][j][r] + bv, g.act);
             }
     }

@@ -262,7 +262,7 @@ __global__ __launch_bounds__(256) void spconv_layer_kernel(const float* __restri
             const float alpha = par[chn], beta = par[COUT + chn];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const size_t row = row0 + 32 * wv + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const size_t row = row0 + 32 * wv + mfma32_row(r, h);
                 if (row < (size_t)n_out) {
                     float v = acc[nb][r] * alpha + beta;
                     if (residual) v += residual[row * COUT + chn];

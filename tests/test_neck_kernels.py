@@ -368,3 +368,42 @@ def test_through_shasta():
     torch.cuda.synchronize()
     assert m1.shape == (B, N, N + 2) and bool(torch.isfinite(m1).all())
     assert torch.equal(m1, r1) and torch.equal(m2, r2)
+
+
+# two chunks (the minimum) with a partial second workgroup whose tile starts mid-row; six chunks: two trips of the steady loop, staging
+# class 12; class 18; a 130-row tile; from 257 columns the rectangular kernels: one chunk, and three (one loop trip + the two-chunk tail)
+K0_CASES = [(1, 8, 5, 37), (2, 24, 3, 180), (1, 16, 2, 256), (1, 8, 140, 1), (1, 8, 5, 257), (1, 24, 6, 290)]
+
+
+@pytest.mark.parametrize("B,cin,H,W", K0_CASES, ids=["%d-%d-%d-%d" % c for c in K0_CASES])
+def test_c3s1_equals_shared_conv_bits(B, cin, H, W):
+    """K0's f32 kernels (csrc/shared_conv.hip, NHWC) and the neck's C3S1 layer at 64 output channels (NCHW) run one convolution body
+    (csrc/conv3x3_f32.hpp) with the pixels as the other MFMA operand: the same fp32 chain per output - the same channel pairs, the same
+    taps, commutative products - and, with a zero convolution bias, the same epilogue.  So the outputs are equal bit for bit, alone
+    and with K0's second map (x_prev / out_prev) in the same launch."""
+    from shasta_amd import hip
+    lib, dev = hip.load(), _dev()
+    g = torch.Generator().manual_seed(77 + cin + H + W)
+    w, bn = layer_tensors(C3S1, cin, 64, g)
+    x, xp = [torch.relu(torch.randn(B, cin, H, W, generator=g)).to(dev) for _ in range(2)]
+    packed = _pack(lib, hip, C3S1, cin, 64, w, bn, dev)
+    want = []
+    for t in (x, xp):
+        rc, out = _run_layer(lib, hip, C3S1, t, packed, 64, 64, 0)
+        assert rc == 0, lib.shasta_last_error()
+        want.append(out.permute(0, 2, 3, 1).contiguous())
+    nbytes = lib.shasta_shared_conv_packed_bytes(cin)
+    assert nbytes > 0
+    k0 = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ts = [t.to(dev).contiguous() for t in [w, torch.zeros(64)] + bn]
+    hip.check(lib.shasta_shared_conv_pack_f32(*[hip.ptr(t) for t in ts], EPS, cin, hip.ptr(k0), nbytes, hip.stream_ptr()),
+              "shasta_shared_conv_pack_f32")
+    alone, got, gotp = [torch.full((B, H, W, 64), SENTINEL, device=dev) for _ in range(3)]
+    s = hip.stream_ptr()
+    hip.check(lib.shasta_shared_conv_f32(hip.ptr(x), None, B, cin, H, W, hip.ptr(k0), hip.ptr(alone), None, s), "shasta_shared_conv_f32")
+    hip.check(lib.shasta_shared_conv_f32(hip.ptr(x), hip.ptr(xp), B, cin, H, W, hip.ptr(k0), hip.ptr(got), hip.ptr(gotp), s),
+              "shasta_shared_conv_f32")
+    torch.cuda.synchronize()
+    assert bool((want[0] > 0).any()) and not torch.equal(want[0], want[1])
+    assert torch.equal(alone, want[0])
+    assert torch.equal(got, want[0]) and torch.equal(gotp, want[1])
