@@ -278,6 +278,36 @@ int shasta_spconv_dense_f32(const float* features, const int* coords, int n, int
                             shasta_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The sparse backbone in train() mode (csrc/bn_rows.hip): BatchNorm1d with BATCH statistics over the feature rows of a level, as the
+ * reference's training step runs it - tools/nusc_shasta/train.py:184-193 freezes backbone and neck and then calls model.train(), so
+ * every BatchNorm1d of `SpMiddleResNetFHD` normalises with the current batch's statistics and updates its running statistics.  The
+ * convolution kernel is the eval one; one (conv, BatchNorm1d) layer is four calls, y = (n, C) fp32 rows, C = 16, 32, 64 or 128:
+ *   1. shasta_spconv_layer_f32 with residual = NULL, relu = 0 on a RAW pack (shasta_spconv_layer_pack_raw_f32: the layout and byte
+ *      count of shasta_spconv_layer_pack_f32 with alpha = 1, beta' = bias, 0 for bias = NULL): y = sum_t W_t x + bias
+ *   2. shasta_bn_rows_stats_f32: mean_m2[0:C] = batch mean, [C:2C] = sum of squared deviations.  Per channel sum and sum of squares in
+ *      float64, one partial per workgroup, combined by one workgroup in a fixed tree: no float atomics, the same bits on every run.  Any
+ *      n >= 1; n = 0 is SHASTA_E_ARG.  workspace: shasta_bn_rows_workspace_bytes(C) bytes (0 for a C that is not served), 8-byte aligned.
+ *   3. shasta_bn_rows_finalize_f32: stat[0:C] = mean, [C:2C] = 1 / sqrt(M2 / n + eps); running statistics (NULL to skip) updated as
+ *      nn.BatchNorm1d does: (1 - momentum) r + momentum new with the unbiased variance M2 / (n - 1), the blend evaluated in float64 and
+ *      rounded once; *num_batches_tracked += 1.  n is an argument of its own (as in shasta_bn_finalize_f32): a synchronised BatchNorm
+ *      can merge (mean, M2, n) over the ranks between steps 2 and 3.
+ *   4. shasta_bn_rows_apply_f32: out = relu?( ((y - mean) invstd) gamma + beta + residual? ), residual (n, C) or NULL.  y, residual and
+ *      out 16-byte aligned; out may alias y or residual (an element is read and written by the same thread); a NaN stays a NaN through
+ *      the ReLU; rows >= n are not written.
+ * shasta_bn_rows_supported(C): 1 for C = 16, 32, 64, 128.  Every other C is SHASTA_E_UNSUPPORTED in steps 2 - 4 before any launch.
+ * ------------------------------------------------------------------------------------------ */
+int shasta_spconv_layer_pack_raw_f32(const float* weight, const float* bias, int Cin, int Cout, int K, void* packed, size_t packed_bytes,
+                                     shasta_stream_t stream);
+int shasta_bn_rows_supported(int C);
+size_t shasta_bn_rows_workspace_bytes(int C);
+int shasta_bn_rows_stats_f32(const float* y, long n, int C, float* mean_m2, void* workspace, size_t workspace_bytes,
+                             shasta_stream_t stream);
+int shasta_bn_rows_finalize_f32(const float* mean_m2, int C, double n, float eps, float momentum, float* stat, float* running_mean,
+                                float* running_var, long* num_batches_tracked, shasta_stream_t stream);
+int shasta_bn_rows_apply_f32(const float* y, long n, int C, const float* stat, const float* gamma, const float* beta,
+                             const float* residual, int relu, float* out, shasta_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * K0 in train() mode (csrc/shared_conv_train.hip): what autograd does for `self.shared_conv(bev_map)` when the reference trains it -
  * tools/nusc_shasta/train.py:183-191 freezes children 1, 2 (backbone, neck) only and keeps every BatchNorm in train mode; the
  * optimizer (:143-147) holds shared_conv.0.{weight,bias} and shared_conv.1.{weight,bias}.  The neck is frozen: no input gradient.

@@ -1,4 +1,5 @@
-"""`SpMiddleResNetFHD`: the sparse 3-D ResNet backbone between the reader and the neck, eval-mode forward on csrc/sparse_conv.hip.
+"""`SpMiddleResNetFHD`: the sparse 3-D ResNet backbone between the reader and the neck, on csrc/sparse_conv.hip: the eval-mode forward,
+and (opt-in, `batch_statistics=True`) the train()-mode forward with batch-statistics BatchNorm1d on csrc/bn_rows.hip.
 
 Mirror of det3d/models/backbones/scn.py:52-211 (`SparseBasicBlock`, `SpMiddleResNetFHD`): same constructor keywords, same sub-module
 names and order, so the `backbone.*` entries of a reference checkpoint load as they are.  spconv (CUDA only) is not imported:
@@ -13,13 +14,24 @@ dense (B, C * D, H, W) map, the dict holds `conv1` .. `conv4` as `SparseLevel` o
 The four neighbour tables of the twenty submanifold convolutions (`res0` .. `res3`) are built once per level; every strided convolution
 has its own.  One host synchronisation per strided level (four per forward): the row count is read back to size the next level.
 
-There is no nn form to fall back on: `train()` mode, a CPU tensor, a norm other than BatchNorm1d and autograd (grad mode on with a
-parameter or the input requiring grad) raise `ShastaHipError`.
+There is no nn form to fall back on: a CPU tensor, a norm other than BatchNorm1d and autograd (grad mode on with a parameter or the
+input requiring grad) raise `ShastaHipError`, and so does `train()` mode unless the module was built with `batch_statistics=True`.
+
+TRAIN() MODE (`batch_statistics=True`, or the attribute set later): the forward of the reference's training step, which freezes the
+backbone but leaves it in train() mode (tools/nusc_shasta/train.py:184-193).  Each (convolution, BatchNorm1d) pair follows torch's
+rule: where `bn.training` is true the layer is the raw convolution into a scratch, the batch statistics of its rows (float64 sums, fixed
+tree: the same bits on every run), a finalize that updates `running_mean`, `running_var` and `num_batches_tracked` of the module in place
+(momentum, unbiased variance), and the apply with ReLU and the block's residual; where it is false the layer is the eval one with the
+running statistics, so a backbone in train() whose BatchNorm modules are all in eval() gives the eval forward's bits.  A module in
+eval() is not affected by the switch.  A level with fewer than 2 rows raises ValueError as torch does; `momentum=None` raises
+`ShastaHipError`.  Levels, row orders and host synchronisations are the eval forward's.  There is no backward: the parameters stay
+frozen (`requires_grad_(False)`) or the call runs under `torch.no_grad()`.
 
 Registration: the class is NOT put into BACKBONES at import (a string config `type="SpMiddleResNetFHD"` stays a KeyError until the
 user decides).  Either pass the class itself, `backbone=dict(type=shasta_amd.backbone.SpMiddleResNetFHD, num_input_features=5,
 ds_factor=8)`, or call `shasta_amd.backbone.register()` once and keep the reference's string configs.
 """
+import ctypes
 import math
 
 import numpy as np
@@ -156,9 +168,10 @@ class _Level:
 
 
 class SpMiddleResNetFHD(nn.Module):
-    def __init__(self, num_input_features=128, norm_cfg=None, name="SpMiddleResNetFHD", **kwargs):
+    def __init__(self, num_input_features=128, norm_cfg=None, name="SpMiddleResNetFHD", batch_statistics=False, **kwargs):
         super().__init__()
         self.name = name
+        self.batch_statistics = bool(batch_statistics)  # serve train() mode with batch-statistics BatchNorm1d (csrc/bn_rows.hip)
         self.dcn = None
         self.zero_init_residual = False
         if norm_cfg is None:
@@ -181,8 +194,10 @@ class SpMiddleResNetFHD(nn.Module):
         self.extra_conv = nn.Sequential(SparseConv3d(128, 128, (3, 1, 1), (2, 1, 1), bias=False), bn(128), nn.ReLU())
 
         # HIP-side state (not parameters, not in state_dict)
-        self._packed = None      # id(conv) -> byte tensor
+        self._packed = None      # id(conv) -> byte tensor: the eval pack (BatchNorm folded with the running statistics)
+        self._packed_raw = None  # id(conv) -> byte tensor: the raw pack (conv + bias) of a layer that runs on batch statistics
         self._packed_key = None
+        self._batch = None       # during a train()-mode forward: id(conv) -> its BatchNorm1d in training mode, and the scratch
 
     # ---- state_dict -----------------------------------------------------------------------------------------
     def _apply(self, fn, *a, **k):  # .to() / .cuda() / .float(): parameter storage moves -> drop the packed layers
@@ -217,9 +232,9 @@ class SpMiddleResNetFHD(nn.Module):
         return ts + [conv.bias] if conv.bias is not None else ts
 
     def _check_servable(self, voxel_features, coors):
-        if self.training:
-            raise hip.ShastaHipError("SpMiddleResNetFHD: train() mode (batch-statistics BatchNorm) is not served: call eval() - the "
-                                     "reference loads this backbone frozen")
+        if self.training and not self.batch_statistics:
+            raise hip.ShastaHipError("SpMiddleResNetFHD: train() mode (batch-statistics BatchNorm) is not served by default: call eval() - "
+                                     "the reference loads this backbone frozen - or build the module with batch_statistics=True")
         if not (voxel_features.is_cuda and coors.is_cuda):
             raise hip.ShastaHipError("SpMiddleResNetFHD: expected device tensors (the HIP path has no CPU fallback)")
         if voxel_features.dtype != torch.float32:
@@ -229,6 +244,9 @@ class SpMiddleResNetFHD(nn.Module):
             if not (isinstance(bn, nn.BatchNorm1d) and bn.affine and bn.track_running_stats):
                 raise hip.ShastaHipError("SpMiddleResNetFHD: only BatchNorm1d with affine parameters and running statistics is served, got %s"
                                          % type(bn).__name__)
+            if self.training and bn.training and bn.momentum is None:
+                raise hip.ShastaHipError("SpMiddleResNetFHD: BatchNorm1d(momentum=None) (cumulative averaging of the running statistics) "
+                                         "is not served in train() mode")
             params += self._tensors(conv, bn)
         if any(t.dtype != torch.float32 for t in params):
             raise hip.ShastaHipError("SpMiddleResNetFHD: fp32 parameters only")
@@ -236,14 +254,24 @@ class SpMiddleResNetFHD(nn.Module):
             raise hip.ShastaHipError("SpMiddleResNetFHD: autograd is not served (no backward): run under torch.no_grad() or freeze the "
                                      "parameters with requires_grad_(False)")
 
-    def _ensure_packed(self, dev):
+    def _batch_layers(self):
+        """id(conv) -> BatchNorm1d of the layers that run on batch statistics in this forward: torch's rule per BatchNorm module."""
+        if not (self.training and self.batch_statistics):
+            return {}
+        return {id(conv): bn for conv, bn in self._pairs() if bn.training}
+
+    def _ensure_packed(self, dev, batch=()):
+        """Eval packs of the layers on running statistics, raw packs of those in `batch`; both kept under one pointer + version key."""
         pairs = self._pairs()
         key = tuple((t.data_ptr(), t._version) for conv, bn in pairs for t in self._tensors(conv, bn)) + (str(dev),)
-        if self._packed is not None and self._packed_key == key:
-            return
+        if self._packed is None or self._packed_key != key:
+            self._packed, self._packed_raw, self._packed_key = {}, {}, key
         lib = hip.load()
-        packed = {}
         for conv, bn in pairs:
+            raw = id(conv) in batch
+            packed = self._packed_raw if raw else self._packed
+            if id(conv) in packed:
+                continue
             k, s, p = conv.geometry
             cin, cout, K = conv.in_channels, conv.out_channels, int(np.prod(k))
             nbytes = lib.shasta_spconv_layer_packed_bytes(cin, cout, K) if lib.shasta_spconv_supported(cin, cout, *k, *s, *p) else 0
@@ -255,12 +283,16 @@ class SpMiddleResNetFHD(nn.Module):
             w, g, b, mean, var = [t.detach().contiguous() for t in self._tensors(conv, bn)[:5]]
             bias = None if conv.bias is None else conv.bias.detach().contiguous()
             buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            hip.check(lib.shasta_spconv_layer_pack_f32(hip.ptr(w), hip.ptr(bias), hip.ptr(g), hip.ptr(b), hip.ptr(mean), hip.ptr(var),
-                                                       float(bn.eps), cin, cout, K, hip.ptr(buf), nbytes, hip.stream_ptr()),
-                      "shasta_spconv_layer_pack_f32")
+            if raw:
+                if not lib.shasta_bn_rows_supported(cout):
+                    raise hip.ShastaHipError("SpMiddleResNetFHD: batch statistics over rows of %d channels are not served" % cout)
+                hip.check(lib.shasta_spconv_layer_pack_raw_f32(hip.ptr(w), hip.ptr(bias), cin, cout, K, hip.ptr(buf), nbytes, hip.stream_ptr()),
+                          "shasta_spconv_layer_pack_raw_f32")
+            else:
+                hip.check(lib.shasta_spconv_layer_pack_f32(hip.ptr(w), hip.ptr(bias), hip.ptr(g), hip.ptr(b), hip.ptr(mean), hip.ptr(var),
+                                                           float(bn.eps), cin, cout, K, hip.ptr(buf), nbytes, hip.stream_ptr()),
+                          "shasta_spconv_layer_pack_f32")
             packed[id(conv)] = buf
-        self._packed = packed
-        self._packed_key = key
 
     # ---- forward --------------------------------------------------------------------------------------------
     @staticmethod
@@ -272,6 +304,8 @@ class SpMiddleResNetFHD(nn.Module):
 
     def _layer(self, x, n_in, nbr, conv, residual=None, relu=True):
         n_out, K = nbr.shape
+        if self._batch is not None and id(conv) in self._batch["bn"]:
+            return self._layer_batch(x, n_in, nbr, conv, residual, relu)
         pk = self._packed[id(conv)]
         out = torch.empty(n_out, conv.out_channels, dtype=torch.float32, device=nbr.device)
         hip.check(hip.load().shasta_spconv_layer_f32(hip.ptr(x), n_in, conv.in_channels, hip.ptr(nbr), n_out, K, hip.ptr(pk), pk.numel(),
@@ -279,10 +313,40 @@ class SpMiddleResNetFHD(nn.Module):
                   "shasta_spconv_layer_f32")
         return out
 
+    def _check_rows(self, conv, n_out):
+        """torch.nn.functional.batch_norm's check for a layer on batch statistics, before any launch of that layer."""
+        if self._batch is not None and id(conv) in self._batch["bn"] and n_out < 2:
+            raise ValueError("Expected more than 1 value per channel when training, got input size %s"
+                             % (torch.Size([n_out, conv.out_channels]),))
+
+    def _layer_batch(self, x, n_in, nbr, conv, residual, relu):
+        """A layer whose BatchNorm1d is in training mode: raw convolution into a scratch, batch statistics of its rows, finalize (updates
+        the module's running statistics in place), apply in place with the residual and the ReLU."""
+        lib = hip.load()
+        bn, st = self._batch["bn"][id(conv)], self._batch
+        n_out, K = nbr.shape
+        C = conv.out_channels
+        self._check_rows(conv, n_out)
+        s = hip.stream_ptr()
+        pk = self._packed_raw[id(conv)]
+        y = torch.empty(n_out, C, dtype=torch.float32, device=nbr.device)
+        hip.check(lib.shasta_spconv_layer_f32(hip.ptr(x), n_in, conv.in_channels, hip.ptr(nbr), n_out, K, hip.ptr(pk), pk.numel(), C, None, 0,
+                                              hip.ptr(y), s), "shasta_spconv_layer_f32")
+        mm, stat, ws = st["mean_m2"], st["stat"], st["workspace"]
+        hip.check(lib.shasta_bn_rows_stats_f32(hip.ptr(y), n_out, C, hip.ptr(mm), hip.ptr(ws), ws.numel(), s), "shasta_bn_rows_stats_f32")
+        hip.check(lib.shasta_bn_rows_finalize_f32(hip.ptr(mm), C, float(n_out), float(bn.eps), float(bn.momentum), hip.ptr(stat),
+                                                  hip.ptr(bn.running_mean), hip.ptr(bn.running_var),
+                                                  ctypes.c_void_p(bn.num_batches_tracked.data_ptr()), s), "shasta_bn_rows_finalize_f32")
+        st["updated"].append(conv)
+        hip.check(lib.shasta_bn_rows_apply_f32(hip.ptr(y), n_out, C, hip.ptr(stat), hip.ptr(bn.weight.detach()), hip.ptr(bn.bias.detach()),
+                                               hip.ptr(residual), 1 if relu else 0, hip.ptr(y), s), "shasta_bn_rows_apply_f32")
+        return y
+
     def _blocks(self, x, lvl, mods):
         for m in mods:
             if not isinstance(m, SparseBasicBlock):
                 continue
+            self._check_rows(m.conv1, lvl.n)
             nbr = lvl.subm_neighbors(m.conv1.geometry)
             h = self._layer(x, lvl.n, nbr, m.conv1)
             x = self._layer(h, lvl.n, nbr, m.conv2, residual=x)
@@ -306,6 +370,7 @@ class SpMiddleResNetFHD(nn.Module):
         n_out = int(count.item())  # the one host synchronisation of this level
         if n_out > cap:
             raise hip.ShastaHipError("SpMiddleResNetFHD: %d output sites from %d rows: the input coordinates are not unique" % (n_out, lvl.n))
+        self._check_rows(conv, n_out)
         out_lvl = _Level(coords[:n_out], lvl.B, grid, index)
         y = self._layer(x, lvl.n, lvl.neighbors(out_lvl.coords, (k, s, p)), conv)
         return out_lvl, y
@@ -321,9 +386,28 @@ class SpMiddleResNetFHD(nn.Module):
         dev = voxel_features.device
         B = int(batch_size)
         grid = tuple(int(v) for v in (np.array(input_shape[::-1]) + [1, 0, 0]))  # sparse_shape, scn.py:181
-        self._ensure_packed(dev)
+        batch = self._batch_layers()
+        self._ensure_packed(dev, batch)
         x = voxel_features.contiguous()
         coords = coors.int().contiguous()
+        if not batch:
+            return self._forward(x, coords, B, grid)
+        width = max(bn.num_features for bn in batch.values())
+        self._batch = dict(bn=batch, updated=[], mean_m2=torch.empty(2 * width, dtype=torch.float32, device=dev),
+                           stat=torch.empty(2 * width, dtype=torch.float32, device=dev),
+                           workspace=torch.empty(lib.shasta_bn_rows_workspace_bytes(width), dtype=torch.uint8, device=dev))
+        try:
+            return self._forward(x, coords, B, grid)
+        finally:
+            # the kernels wrote the running statistics through raw pointers (no version bump): an eval pack folded from the old ones,
+            # left by an earlier forward under the same key, is stale now
+            for conv in self._batch["updated"]:
+                self._packed.pop(id(conv), None)
+            self._batch = None
+
+    def _forward(self, x, coords, B, grid):
+        lib = hip.load()
+        dev = x.device
         V = int(x.shape[0])
 
         index = self._index_buffer(B, grid, V, dev)
@@ -331,6 +415,7 @@ class SpMiddleResNetFHD(nn.Module):
                   "shasta_spconv_index_rows")
         lvl = _Level(coords, B, grid, index)
         conv0 = self.conv_input[0]
+        self._check_rows(conv0, V)
         x = self._layer(x, V, lvl.subm_neighbors(conv0.geometry), conv0)
         x = self._blocks(x, lvl, self.conv1)
         levels = {"conv1": SparseLevel(x, lvl.coords, lvl.grid, B)}

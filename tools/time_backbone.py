@@ -3,9 +3,11 @@ density -> VoxelGenerator.generate_batch_device (0.075 m x 0.075 m x 0.2 m voxel
 (what the reader computes) -> backbone.  HIP events around every C call after a warm-up, summed per level into index build (bitmap,
 scan, coordinates, neighbour tables), convolutions and the densify; next to them the rows per level, the share of taps present, and a
 floor from the counted present taps: their FLOP at the f32 matrix peak and the bytes gathered, read and written at the measured HBM rate.
-One JSON line per batch size.
+One JSON line per batch size.  With --train the same input goes through the train()-mode forward (batch_statistics=True, every
+BatchNorm1d on batch statistics, csrc/bn_rows.hip): the convolutions then write raw sums, and the statistics, finalize and apply calls of a
+level are listed next to them.
 
-    python tools/time_backbone.py [--batches 1 2] [--iters 5] [--points 300000]
+    python tools/time_backbone.py [--batches 1 2] [--iters 5] [--points 300000] [--train]
 """
 import argparse
 import json
@@ -22,6 +24,9 @@ from shasta_amd.voxel_generator import VoxelGenerator  # noqa: E402
 F32_MATRIX_PEAK = 155e12  # FLOP/s, v_mfma_f32_*_f32 measured
 HBM_RATE = 6.29e12        # B/s, measured float4 copy
 INDEX_CALLS = ("shasta_spconv_index_rows", "shasta_spconv_out_coords", "shasta_spconv_neighbors")
+# column of a level's timing row per call: index, conv, and the three batch-statistics calls of the train()-mode forward
+COLUMNS = dict({n: 0 for n in INDEX_CALLS}, shasta_spconv_layer_f32=1, shasta_bn_rows_stats_f32=2, shasta_bn_rows_finalize_f32=3,
+               shasta_bn_rows_apply_f32=4)
 
 
 def cloud(rng, P):
@@ -36,14 +41,14 @@ def cloud(rng, P):
 
 
 class TimingLib:
-    """The loaded library with an event pair around every spconv call."""
+    """The loaded library with an event pair around every spconv and bn_rows call."""
 
     def __init__(self, lib):
         self._lib, self.calls = lib, []
 
     def __getattr__(self, name):
         fn = getattr(self._lib, name)
-        if not name.startswith("shasta_spconv_") or name.endswith(("_bytes", "_supported")):
+        if not name.startswith(("shasta_spconv_", "shasta_bn_rows_")) or name.endswith(("_bytes", "_supported")):
             return fn
 
         def timed(*a):
@@ -57,16 +62,14 @@ class TimingLib:
 
 
 def per_level(calls):
-    """Calls in forward order -> [index ms, conv ms] per level (a level starts at its out_coords call), densify ms."""
-    levels, dense = [[0.0, 0.0]], 0.0
+    """Calls in forward order -> [index, conv, stats, finalize, apply] ms per level (a level starts at its out_coords call), densify ms."""
+    levels, dense = [[0.0] * 5], 0.0
     for name, e0, e1 in calls:
         ms = e0.elapsed_time(e1)
         if name == "shasta_spconv_out_coords":
-            levels.append([0.0, 0.0])
-        if name in INDEX_CALLS:
-            levels[-1][0] += ms
-        elif name == "shasta_spconv_layer_f32":
-            levels[-1][1] += ms
+            levels.append([0.0] * 5)
+        if name in COLUMNS:
+            levels[-1][COLUMNS[name]] += ms
         elif name == "shasta_spconv_dense_f32":
             dense += ms
     return levels, dense
@@ -77,10 +80,11 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 2])
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--points", type=int, default=300000)
+    ap.add_argument("--train", action="store_true", help="time the train()-mode forward (batch-statistics BatchNorm1d)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
-    m = backbone.SpMiddleResNetFHD(num_input_features=5, ds_factor=8).eval().to(dev)
+    m = backbone.SpMiddleResNetFHD(num_input_features=5, ds_factor=8, batch_statistics=a.train).train(a.train).to(dev)
     vg = VoxelGenerator([0.075, 0.075, 0.2], [-54, -54, -5, 54, 54, 3], 10, max_voxels=160000)
     shape = vg.grid_size.tolist()
     rng = np.random.default_rng(0)
@@ -123,7 +127,7 @@ def main():
         acc = None
         for it in range(a.iters):
             lv, dn = per_level(tl.calls[it * n_calls:(it + 1) * n_calls])
-            flat = [v for pair in lv for v in pair] + [dn]
+            flat = [v for row in lv for v in row] + [dn]
             acc = flat if acc is None else [x + y for x, y in zip(acc, flat)]
         acc = [v / a.iters for v in acc]
         # the convolutions of a level: conv1 has 5 (conv_input + two blocks), conv2..4 have 5 (strided + two blocks), the last level 1
@@ -136,10 +140,16 @@ def main():
             byts = sum(4 * (s["present"] * s["cin"] + s["n_out"] * s["K"] + s["n_out"] * s["cout"] * (2 if s["residual"] else 1)
                             + s["K"] * s["cin"] * s["cout"]) for s in ss)
             taps = sum(s["present"] for s in ss) / max(1, sum(s["n_out"] * s["K"] for s in ss))
-            out_levels.append(dict(level=name, rows=ss[-1]["n_out"], taps_present=round(taps, 3), index_ms=round(acc[2 * i], 4),
-                                   conv_ms=round(acc[2 * i + 1], 4), gflop=round(flop / 1e9, 3), mbytes=round(byts / 1e6, 2),
-                                   floor_flop_ms=round(flop / F32_MATRIX_PEAK * 1e3, 4), floor_bytes_ms=round(byts / HBM_RATE * 1e3, 4)))
-        print(json.dumps(dict(tool="time_backbone", B=B, points_per_cloud=a.points, voxels=sum(nv), grid=[shape[2] + 1, shape[1], shape[0]],
+            row = dict(level=name, rows=ss[-1]["n_out"], taps_present=round(taps, 3), index_ms=round(acc[5 * i], 4),
+                       conv_ms=round(acc[5 * i + 1], 4), gflop=round(flop / 1e9, 3), mbytes=round(byts / 1e6, 2),
+                       floor_flop_ms=round(flop / F32_MATRIX_PEAK * 1e3, 4), floor_bytes_ms=round(byts / HBM_RATE * 1e3, 4))
+            if a.train:
+                # the three passes over a layer's (rows, Cout) scratch: read; -; read + residual read + write
+                bn_bytes = sum(4 * s["n_out"] * s["cout"] * (3 + (1 if s["residual"] else 0)) for s in ss)
+                row.update(stats_ms=round(acc[5 * i + 2], 4), finalize_ms=round(acc[5 * i + 3], 4), apply_ms=round(acc[5 * i + 4], 4),
+                           bn_mbytes=round(bn_bytes / 1e6, 2), bn_floor_bytes_ms=round(bn_bytes / HBM_RATE * 1e3, 4))
+            out_levels.append(row)
+        print(json.dumps(dict(tool="time_backbone", mode="train" if a.train else "eval", B=B, points_per_cloud=a.points, voxels=sum(nv), grid=[shape[2] + 1, shape[1], shape[0]],
                               forward_ms=round(total, 3), device_ms=round(sum(acc), 3), dense_ms=round(acc[-1], 4),
                               result=list(ret.shape), levels=out_levels, device=torch.cuda.get_device_name(0))), flush=True)
 
