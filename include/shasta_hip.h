@@ -308,6 +308,41 @@ int shasta_bn_rows_apply_f32(const float* y, long n, int C, const float* stat, c
                              const float* residual, int relu, float* out, shasta_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The RPN neck in train() mode (csrc/bn_maps.hip, csrc/neck.hip): BatchNorm2d with BATCH statistics over fp32 NCHW maps, as the
+ * reference's training step runs the frozen neck (tools/nusc_shasta/train.py:184-193).  The tensor y is addressed like a neck layer's
+ * output, (y, B, C, plane = OH * OW, channels_total, channel_offset): channel c of image b is the `plane` contiguous floats at
+ * ((b * channels_total + channel_offset + c) * plane); the calls read and write channels [channel_offset, channel_offset + C) and touch
+ * no other float (the deblocks keep writing their halves of the concatenated map in place).  y is 16-byte aligned; C is a multiple of
+ * 32 (every Cout shasta_neck_layer_supported accepts), B and C <= 65535.  One (conv, BatchNorm2d) layer is four calls:
+ *   1. shasta_neck_layer_raw_f32: the arguments and the packed buffer of shasta_neck_layer_f32 - it reads the weight section only and
+ *      ignores alpha / beta' - and y = conv(x) as it is: no affine, no ReLU.  The same kernels (a second instantiation), tiling, launch
+ *      plan and refusals as the eval call.
+ *   2. shasta_bn_maps_stats_f32: mean_m2[0:C] = batch mean, [C:2C] = sum of squared deviations over the n = B * plane values of each
+ *      channel.  Per channel sum and sum of squares in float64, one partial per workgroup, combined by one workgroup in a fixed tree;
+ *      the division of the work depends on (B, C, plane) only; no float atomics: the same bits on every run.  Planes with
+ *      plane % 4 != 0 (starts only 4-byte aligned) take a scalar form.  n = 0 is SHASTA_E_ARG.  workspace:
+ *      shasta_bn_maps_workspace_bytes(B, C, plane) bytes (0 for a C that is not served), 8-byte aligned.
+ *   3. shasta_bn_maps_finalize_f32: the semantics of shasta_bn_rows_finalize_f32 (one shared device routine): stat[0:C] = mean,
+ *      [C:2C] = 1 / sqrt(M2 / n + eps); running statistics (NULL to skip) updated as nn.BatchNorm2d does: (1 - momentum) r + momentum new
+ *      with the unbiased variance M2 / (n - 1), the blend evaluated in float64 and rounded once; *num_batches_tracked += 1.  n is an
+ *      argument of its own: a synchronised BatchNorm can merge (mean, M2, n) over the ranks between steps 2 and 3.
+ *   4. shasta_bn_maps_apply_f32: in place on the slice, y = relu?( ((y - mean) invstd) gamma + beta ) - the order of operations of
+ *      shasta_bn_rows_apply_f32; a NaN stays a NaN through the ReLU.
+ * Every refusal (null pointer, a slice that leaves the tensor, the grid limit, SHASTA_E_UNSUPPORTED for other widths, a short
+ * workspace) is made before any launch.
+ * ------------------------------------------------------------------------------------------ */
+int shasta_neck_layer_raw_f32(const float* x, int B, int Cin, int H, int W, const void* packed, size_t packed_bytes, int kind, int Cout,
+                              float* out, int out_channels_total, int out_channel_offset, shasta_stream_t stream);
+int shasta_bn_maps_supported(int C);
+size_t shasta_bn_maps_workspace_bytes(int B, int C, long plane);
+int shasta_bn_maps_stats_f32(const float* y, int B, int C, long plane, int channels_total, int channel_offset, float* mean_m2,
+                             void* workspace, size_t workspace_bytes, shasta_stream_t stream);
+int shasta_bn_maps_finalize_f32(const float* mean_m2, int C, double n, float eps, float momentum, float* stat, float* running_mean,
+                                float* running_var, long* num_batches_tracked, shasta_stream_t stream);
+int shasta_bn_maps_apply_f32(float* y, int B, int C, long plane, int channels_total, int channel_offset, const float* stat,
+                             const float* gamma, const float* beta, int relu, shasta_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * K0 in train() mode (csrc/shared_conv_train.hip): what autograd does for `self.shared_conv(bev_map)` when the reference trains it -
  * tools/nusc_shasta/train.py:183-191 freezes children 1, 2 (backbone, neck) only and keeps every BatchNorm in train mode; the
  * optimizer (:143-147) holds shared_conv.0.{weight,bias} and shared_conv.1.{weight,bias}.  The neck is frozen: no input gradient.

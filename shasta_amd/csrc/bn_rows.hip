@@ -13,7 +13,7 @@
 // beg + g, beg + g + G, .. of channel c in order, the G group sums are then added in order.  The slices: at least BNR_ROWS_MIN rows each,
 // BNR_SLICES at most (both ends are seams: n below one slice, n where the slice count saturates; a slice may be empty - per = ceil(n /
 // slices) can leave the last workgroups without rows - and then contributes exact zeros).
-#include "common.hpp"
+#include "bn_finalize.hpp"
 
 namespace shasta {
 
@@ -103,20 +103,13 @@ __global__ __launch_bounds__(1024) void bn_rows_combine_kernel(const double* __r
     }
 }
 
-// mean / M2 / n of the whole batch -> what the normalisation uses (mean, 1 / sqrt(biased variance + eps)) and the running statistics as
-// nn.BatchNorm1d keeps them ((1 - m) r + m new, unbiased variance); the blend is evaluated in float64 and rounded once
+// mean / M2 / n of the whole batch -> stat and the running statistics as nn.BatchNorm1d keeps them (bn_finalize.hpp)
 __global__ __launch_bounds__(128) void bn_rows_finalize_kernel(const float* __restrict__ mean_m2, int C, double n, float eps, float momentum,
                                                                float* __restrict__ stat, float* __restrict__ running_mean,
                                                                float* __restrict__ running_var, long* __restrict__ nbt) {
     const int c = threadIdx.x;
     if (c >= C) return;
-    const float mean = mean_m2[c], m2 = mean_m2[C + c];
-    const float var = (float)((double)m2 / n);
-    stat[c] = mean;
-    stat[C + c] = 1.0f / sqrtf(var + eps);
-    const double m = (double)momentum;
-    if (running_mean) running_mean[c] = (float)((1.0 - m) * (double)running_mean[c] + m * (double)mean);
-    if (running_var) running_var[c] = (float)((1.0 - m) * (double)running_var[c] + m * ((double)m2 / (n > 1.0 ? n - 1.0 : 1.0)));
+    bn_finalize_channel(mean_m2, C, c, n, eps, momentum, stat, running_mean, running_var);
     if (nbt && c == 0) nbt[0] += 1;
 }
 

@@ -23,6 +23,8 @@
 //   C1 / D2                32   49 152                  32                     106 + 48      3
 //   C3S1 flat (W <= 256)    4   2048 IN_PT + 18 432     36                     IN_PT 8: 97 + 32 (3), 12: 120 + 32 (3), 14: 132 + 32 (3),
 //     (IN_PT by map width: W = 90 -> 8, W = 180 -> 12)                         16: 145 + 32 (2), 18: 159 + 32 (2)
+// Every kernel has a second, RAW instantiation for train() mode (shasta_neck_layer_raw_f32: the accumulator stored as it is, bn_maps.hip
+// takes the batch statistics and normalises afterwards): the same registers and waves per SIMD, C1 / D2 112 + 48 (3), no scratch.
 //
 // Packed layer: [virtual 64-channel block vb][Cin rounded up to CK][tap][64] weights (a straight copy per chunk; channels >= Cout and
 // >= Cin are zeros), then alpha[Cout rounded up to 64], beta'[same]: alpha = gamma / sqrt(var + eps), beta' = beta - mean * alpha,
@@ -73,7 +75,9 @@ __global__ void neck_pack_kernel(const float* __restrict__ w, const float* __res
     }
 }
 
-// D[channel][pixel]: channels cb * 64 + 32 nb + mfma32_row(r, h) < Cout of the lane's pixel at o, `plane` floats from channel to channel
+// D[channel][pixel]: channels cb * 64 + 32 nb + mfma32_row(r, h) < Cout of the lane's pixel at o, `plane` floats from channel to channel.
+// RAW (train() mode, bn_maps.hip normalises afterwards): the accumulator as it is - no affine, no ReLU, par not read.
+template <bool RAW>
 __device__ __forceinline__ void neck_epilogue(const f32x16& acc0, const f32x16& acc1, const float* par, int cout_pad, int cb, int Cout,
                                               float* o, size_t plane) {
     const int h = (threadIdx.x & 63) >> 5;
@@ -84,15 +88,19 @@ __device__ __forceinline__ void neck_epilogue(const f32x16& acc0, const f32x16& 
             const int chn = cb * 64 + nb * 32 + mfma32_row(r, h);
             if (chn < Cout) {
                 const float a = nb ? acc1[r] : acc0[r];
-                const float v = a * par[chn] + par[cout_pad + chn];
-                o[(size_t)chn * plane] = relu_nan(v);
+                if constexpr (RAW) {
+                    o[(size_t)chn * plane] = a;
+                } else {
+                    const float v = a * par[chn] + par[cout_pad + chn];
+                    o[(size_t)chn * plane] = relu_nan(v);
+                }
             }
         }
     }
 }
 
 // PH x PW: the pixel domain (H/2 x W/2 for C3S2, else H x W).  nchunk = cin_pad / CK; blocks = neck_blocks().
-template <int KIND>
+template <int KIND, bool RAW>
 __global__ __launch_bounds__(256) void neck_layer_kernel(const float* __restrict__ x, const float* __restrict__ packed,
                                                          float* __restrict__ out, int Cin, int H, int W, int Cout, int PH, int PW,
                                                          int ctot, int coff, int blocks, int nchunk) {
@@ -109,12 +117,12 @@ __global__ __launch_bounds__(256) void neck_layer_kernel(const float* __restrict
     const int OH = KIND == 3 ? 2 * H : PH, OW = KIND == 3 ? 2 * W : PW;
     const int oy = KIND == 3 ? 2 * py + (q >> 1) : py, ox = KIND == 3 ? 2 * px + (q & 1) : px;
     const size_t oplane = (size_t)OH * OW;
-    neck_epilogue(acc0, acc1, packed + (size_t)blocks * nchunk * G::WT, ncb * 64, cb, Cout,
-                  out + ((size_t)b * ctot + coff) * oplane + (size_t)oy * OW + ox, oplane);
+    neck_epilogue<RAW>(acc0, acc1, packed + (size_t)blocks * nchunk * G::WT, ncb * 64, cb, Cout,
+                       out + ((size_t)b * ctot + coff) * oplane + (size_t)oy * OW + ox, oplane);
 }
 
 // C3S1 up to 256 columns: the flattened-pixel form, two load chunks ahead (the [Cin][9][64] weights of a channel block read as [Cin/4][36][64])
-template <int IN_PT>
+template <int IN_PT, bool RAW>
 __global__ __launch_bounds__(256) void neck_c3s1_flat_kernel(const float* __restrict__ x, const float* __restrict__ packed,
                                                              float* __restrict__ out, int Cin, int H, int W, int Cout, int ctot, int coff,
                                                              int blocks) {
@@ -124,7 +132,7 @@ __global__ __launch_bounds__(256) void neck_c3s1_flat_kernel(const float* __rest
     f32x16 acc0, acc1;
     conv_body<false, 2>(ConvFlatTile<IN_PT>(H, W), x + (size_t)b * Cin * npix, packed + (size_t)cb * Cin * 9 * 64, Cin, H, W, Cin / 4, acc0, acc1);
     if (pp >= npix) return;
-    neck_epilogue(acc0, acc1, packed + (size_t)blocks * Cin * 9 * 64, blocks * 64, cb, Cout, out + ((size_t)b * ctot + coff) * npix + pp, npix);
+    neck_epilogue<RAW>(acc0, acc1, packed + (size_t)blocks * Cin * 9 * 64, blocks * 64, cb, Cout, out + ((size_t)b * ctot + coff) * npix + pp, npix);
 }
 
 static bool neck_shape_ok(int kind, int Cin, int Cout, int H, int W) {
@@ -169,8 +177,10 @@ extern "C" int shasta_neck_layer_pack_f32(const float* weight, const float* bn_w
     return check_launch("neck_layer_pack");
 }
 
-extern "C" int shasta_neck_layer_f32(const float* x, int B, int Cin, int H, int W, const void* packed, size_t packed_bytes, int kind,
-                                     int Cout, float* out, int out_channels_total, int out_channel_offset, shasta_stream_t stream) {
+// The checks and the launch plan of a layer, shared by the eval entry point and the raw one (RAW: the same packed buffer, weights only)
+template <bool RAW>
+static int neck_layer_run(const float* x, int B, int Cin, int H, int W, const void* packed, size_t packed_bytes, int kind, int Cout, float* out,
+                          int out_channels_total, int out_channel_offset, shasta_stream_t stream) {
     SHASTA_REQUIRE(x && packed && out, "neck_layer: null pointer");
     SHASTA_REQUIRE(B >= 0, "neck_layer: bad batch size");
     if (!neck_shape_ok(kind, Cin, Cout, H, W)) {
@@ -200,13 +210,13 @@ extern "C" int shasta_neck_layer_f32(const float* x, int B, int Cin, int H, int 
     const ConvFlatPlan plan = conv_flat_plan(H, W);
     if (kind == 0 && plan.fits) {
         conv_flat_dispatch(plan.in_pt, [&](auto pt) {
-            hipLaunchKernelGGL(neck_c3s1_flat_kernel<decltype(pt)::value>, dim3(cdiv(H * W, 128), 1, B * blocks), dim3(256), plan.lds,
+            hipLaunchKernelGGL((neck_c3s1_flat_kernel<decltype(pt)::value, RAW>), dim3(cdiv(H * W, 128), 1, B * blocks), dim3(256), plan.lds,
                                as_stream(stream), x, pk, out, Cin, H, W, Cout, out_channels_total, out_channel_offset, blocks);
         });
         return check_launch("neck_layer_flat");
     }
 #define SHASTA_NECK_LAUNCH(K) \
-    hipLaunchKernelGGL(neck_layer_kernel<K>, grid, dim3(256), 0, as_stream(stream), x, pk, out, Cin, H, W, Cout, PH, PW, out_channels_total, \
+    hipLaunchKernelGGL((neck_layer_kernel<K, RAW>), grid, dim3(256), 0, as_stream(stream), x, pk, out, Cin, H, W, Cout, PH, PW, out_channels_total, \
                        out_channel_offset, blocks, nchunk)
     if (kind == 0) SHASTA_NECK_LAUNCH(0);
     else if (kind == 1) SHASTA_NECK_LAUNCH(1);
@@ -214,4 +224,14 @@ extern "C" int shasta_neck_layer_f32(const float* x, int B, int Cin, int H, int 
     else SHASTA_NECK_LAUNCH(3);
 #undef SHASTA_NECK_LAUNCH
     return check_launch("neck_layer");
+}
+
+extern "C" int shasta_neck_layer_f32(const float* x, int B, int Cin, int H, int W, const void* packed, size_t packed_bytes, int kind,
+                                     int Cout, float* out, int out_channels_total, int out_channel_offset, shasta_stream_t stream) {
+    return neck_layer_run<false>(x, B, Cin, H, W, packed, packed_bytes, kind, Cout, out, out_channels_total, out_channel_offset, stream);
+}
+
+extern "C" int shasta_neck_layer_raw_f32(const float* x, int B, int Cin, int H, int W, const void* packed, size_t packed_bytes, int kind,
+                                         int Cout, float* out, int out_channels_total, int out_channel_offset, shasta_stream_t stream) {
+    return neck_layer_run<true>(x, B, Cin, H, W, packed, packed_bytes, kind, Cout, out, out_channels_total, out_channel_offset, stream);
 }

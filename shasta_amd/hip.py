@@ -89,6 +89,12 @@ SYMBOLS = {
     "shasta_bn_rows_stats_f32": (_I, [_P, C.c_long, _I, _P, _P, _Z, _P]),
     "shasta_bn_rows_finalize_f32": (_I, [_P, _I, C.c_double, _F, _F, _P, _P, _P, _P, _P]),
     "shasta_bn_rows_apply_f32": (_I, [_P, C.c_long, _I, _P, _P, _P, _P, _I, _P, _P]),
+    "shasta_neck_layer_raw_f32": (_I, [_P, _I, _I, _I, _I, _P, _Z, _I, _I, _P, _I, _I, _P]),
+    "shasta_bn_maps_supported": (_I, [_I]),
+    "shasta_bn_maps_workspace_bytes": (_Z, [_I, _I, C.c_long]),
+    "shasta_bn_maps_stats_f32": (_I, [_P, _I, _I, C.c_long, _I, _I, _P, _P, _Z, _P]),
+    "shasta_bn_maps_finalize_f32": (_I, [_P, _I, C.c_double, _F, _F, _P, _P, _P, _P, _P]),
+    "shasta_bn_maps_apply_f32": (_I, [_P, _I, _I, C.c_long, _I, _I, _P, _P, _P, _I, _P]),
     "shasta_conv_train_supported": (_I, [_I, _I, _I]),
     "shasta_shared_conv_pack_raw_f32": (_I, [_P, _P, _I, _P, _Z, _P]),
     "shasta_shared_conv_pack_raw_f16x2": (_I, [_P, _P, _I, _P, _Z, _P]),

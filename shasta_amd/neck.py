@@ -11,9 +11,23 @@ order (module creation order = RNG order, so a seeded default init gives the ref
     (no pass for `torch.cat`).  After a warm-up call there is no host synchronisation and no allocation but the result: the call can
     be captured in `torch.cuda.graph`.  A CPU tensor on this path raises: there is no CPU fallback.
   * `forward_layers` - the module's own nn layers, the reference's `forward` restated - for everything outside that set: `train()`
-    mode (the reference keeps the frozen neck's BatchNorms on batch statistics while training, tools/nusc_shasta/train.py:193),
-    autograd on, other norms, other strides, other dtypes.  The same arrangement as shared_conv's documented exceptions.
+    mode by default (the reference keeps the frozen neck's BatchNorms on batch statistics while training,
+    tools/nusc_shasta/train.py:193), autograd on, other norms, other strides, other dtypes.  The same arrangement as shared_conv's
+    documented exceptions.
+
+TRAIN() MODE ON THE KERNELS (`batch_statistics=True`, or the attribute set later; the default keeps `forward_layers`): with autograd
+off or nothing requiring grad, a `train()`-mode call takes the kernel path too.  torch's rule per layer: where `bn.training` is true
+the layer is four calls into its destination (a ping-pong buffer or the output slice) - `shasta_neck_layer_raw_f32` (the eval kernels
+without the epilogue's affine and ReLU, reading the weight section of the SAME packed buffer: nothing is re-packed per step),
+`shasta_bn_maps_stats_f32` (float64 sums, fixed tree: the same bits on every run), `shasta_bn_maps_finalize_f32` (updates
+`running_mean`, `running_var`, `num_batches_tracked` of the module in place: momentum, unbiased variance) and `shasta_bn_maps_apply_f32`
+(in place); where it is false the layer is the eval one.  The kernels write the running statistics through raw pointers, which bumps no
+version counter, so a forward marks the alpha / beta' of the layers it updated as stale and the next eval use re-packs them.  The
+statistics workspace and the `stat` buffers live with the ping-pong buffers: no host synchronisation, no allocation but the result,
+capturable.  `n = B * OH * OW < 2` raises ValueError as torch does; `momentum=None` raises `ShastaHipError`.
 """
+import ctypes
+
 import numpy as np
 import torch
 from torch import nn
@@ -50,8 +64,9 @@ def build_norm_layer(cfg, num_features):
 @NECKS.register_module
 class RPN(nn.Module):
     def __init__(self, layer_nums, ds_layer_strides, ds_num_filters, us_layer_strides, us_num_filters, num_input_features,
-                 norm_cfg=None, name="rpn", logger=None, **kwargs):
+                 norm_cfg=None, name="rpn", logger=None, batch_statistics=False, **kwargs):
         super().__init__()
+        self.batch_statistics = bool(batch_statistics)  # serve train() mode with batch-statistics BatchNorm2d (csrc/bn_maps.hip)
         self._layer_strides = ds_layer_strides
         self._num_filters = ds_num_filters
         self._layer_nums = layer_nums
@@ -90,8 +105,10 @@ class RPN(nn.Module):
 
         # HIP-side state (not parameters, not in state_dict)
         self._packed = None      # one byte tensor per layer
-        self._packed_key = None
+        self._packed_key = None  # one (pointer, version) key per layer
+        self._stale = set()      # layers whose running statistics the kernels wrote: weights packed, alpha / beta' out of date
         self._bufs = None        # the two ping-pong buffers
+        self._train_bufs = None  # train() mode: mean_m2, stat, the statistics workspace
         self._plan = self._make_plan()
 
     def _make_layer(self, inplanes, planes, num_blocks, stride=1):
@@ -173,18 +190,24 @@ class RPN(nn.Module):
         """Forget the packed layers; the next kernel-path forward re-packs them.  They follow in-place writes, optimizer steps and
         load_state_dict by themselves (pointer + version checks); call this after a write that bumps no version counter."""
         self._packed_key = None
+        self._stale = set()
 
     @staticmethod
     def _tensors(conv, bn):
         return [conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var]
 
-    def _ensure_packed(self, dev):
-        key = tuple((t.data_ptr(), t._version) for _, conv, bn, _ in self._plan for t in self._tensors(conv, bn)) + (str(dev),)
-        if self._packed is not None and self._packed_key == key:
-            return
+    def _ensure_packed(self, dev, batch=()):
+        """Every layer packed for its tensors as they are (pointer + version key per layer).  A layer in `batch` (it runs on batch
+        statistics in this forward) reads the weight section only, so alpha / beta' marked stale by an earlier train() forward do not
+        make it re-pack; every other layer is re-packed when stale."""
+        if self._packed is None or self._packed_key is None:
+            self._packed, self._packed_key, self._stale = [None] * len(self._plan), [None] * len(self._plan), set()
         lib = hip.load()
-        packed = []
-        for kind, conv, bn, _ in self._plan:
+        packed = self._packed
+        for i, (kind, conv, bn, _) in enumerate(self._plan):
+            key = tuple((t.data_ptr(), t._version) for t in self._tensors(conv, bn)) + (str(dev),)
+            if packed[i] is not None and self._packed_key[i] == key and (i in batch or i not in self._stale):
+                continue
             ts = [t.detach().contiguous() for t in self._tensors(conv, bn)]
             cin, cout = conv.in_channels, conv.out_channels
             if kind == C1:  # the reference's 1x1 deblock is a Conv2d, (Cout, Cin, 1, 1); the C1 kind takes ConvTranspose2d's (Cin, Cout, 1, 1)
@@ -195,9 +218,8 @@ class RPN(nn.Module):
             buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             hip.check(lib.shasta_neck_layer_pack_f32(*[hip.ptr(t) for t in ts], float(bn.eps), kind, cin, cout, hip.ptr(buf), nbytes,
                                                      hip.stream_ptr()), "shasta_neck_layer_pack_f32")
-            packed.append(buf)
-        self._packed = packed
-        self._packed_key = key
+            packed[i], self._packed_key[i] = buf, key
+            self._stale.discard(i)
 
     def _shapes(self, H, W):
         """Per layer of the plan: (H, W) of its input and of its output; None when a layer is not served at this map size."""
@@ -218,8 +240,40 @@ class RPN(nn.Module):
                 out_hw = (oh, ow)
         return shapes
 
+    def _batch_layers(self, B, shapes):
+        """Indices of the plan's layers that run on batch statistics in this forward: torch's rule per BatchNorm module.  torch's
+        refusals for them are made here, before any launch."""
+        if not (self.training and self.batch_statistics):
+            return frozenset()
+        lib = hip.load()
+        batch = []
+        for i, ((_, conv, bn, _), s) in enumerate(zip(self._plan, shapes)):
+            if not bn.training:
+                continue
+            if bn.momentum is None:
+                raise hip.ShastaHipError("RPN: BatchNorm2d(momentum=None) (cumulative averaging of the running statistics) is not served "
+                                         "in train() mode")
+            if B * s[2] * s[3] < 2:
+                raise ValueError("Expected more than 1 value per channel when training, got input size %s"
+                                 % (torch.Size([B, conv.out_channels, s[2], s[3]]),))
+            if not lib.shasta_bn_maps_supported(conv.out_channels):
+                raise hip.ShastaHipError("RPN: batch statistics over maps of %d channels are not served" % conv.out_channels)
+            batch.append(i)
+        return frozenset(batch)
+
+    def _ensure_train_bufs(self, B, shapes, batch, dev):
+        lib = hip.load()
+        cmax = max(self._plan[i][1].out_channels for i in batch)
+        need = max(lib.shasta_bn_maps_workspace_bytes(B, self._plan[i][1].out_channels, shapes[i][2] * shapes[i][3]) for i in batch)
+        tb = self._train_bufs
+        if tb is None or tb[0].device != dev or tb[0].numel() < 2 * cmax or tb[2].numel() < need:
+            self._train_bufs = None
+            tb = self._train_bufs = (torch.empty(2 * cmax, dtype=torch.float32, device=dev), torch.empty(2 * cmax, dtype=torch.float32, device=dev),
+                                     torch.empty(need, dtype=torch.uint8, device=dev))
+        return tb
+
     def _kernel_path(self, x):
-        if self.training or self._plan is None or x.dim() != 4 or x.dtype != torch.float32:
+        if (self.training and not self.batch_statistics) or self._plan is None or x.dim() != 4 or x.dtype != torch.float32:
             return False
         params = [t for _, conv, bn, _ in self._plan for t in self._tensors(conv, bn)]
         if any(t.dtype != torch.float32 for t in params):
@@ -241,7 +295,8 @@ class RPN(nn.Module):
             return self.forward_layers(x)
         lib = hip.load()
         dev = x.device
-        self._ensure_packed(dev)
+        batch = self._batch_layers(B, shapes)
+        self._ensure_packed(dev, batch)
         x = x.contiguous()
         need = max([B * conv.out_channels * s[2] * s[3] for (_, conv, _, role), s in zip(self._plan, shapes) if role == "block"])
         if self._bufs is None or self._bufs[0].numel() < need or self._bufs[0].device != dev:
@@ -252,14 +307,30 @@ class RPN(nn.Module):
         oh, ow = next(s[2:] for (_, _, _, role), s in zip(self._plan, shapes) if role != "block")
         out = torch.empty(B, ctot, oh, ow, dtype=torch.float32, device=dev)
         stream = hip.stream_ptr()
+        if batch:
+            mm, stat, ws = self._ensure_train_bufs(B, shapes, batch, dev)
         cur, nxt = x, 0
-        for (kind, conv, _, role), pk, s in zip(self._plan, self._packed, shapes):
+        for i, ((kind, conv, bn, role), pk, s) in enumerate(zip(self._plan, self._packed, shapes)):
             if role == "block":
                 dst, total, off = self._bufs[nxt], conv.out_channels, 0
             else:
                 dst, total, off = out, ctot, int(offs[role])
-            hip.check(lib.shasta_neck_layer_f32(hip.ptr(cur), B, conv.in_channels, s[0], s[1], hip.ptr(pk), pk.numel(), kind,
-                                                conv.out_channels, hip.ptr(dst), total, off, stream), "shasta_neck_layer_f32")
+            args = (hip.ptr(cur), B, conv.in_channels, s[0], s[1], hip.ptr(pk), pk.numel(), kind, conv.out_channels, hip.ptr(dst), total, off,
+                    stream)
+            if i in batch:  # raw convolution into the destination, batch statistics of it, finalize, apply in place
+                C, plane = conv.out_channels, s[2] * s[3]
+                hip.check(lib.shasta_neck_layer_raw_f32(*args), "shasta_neck_layer_raw_f32")
+                hip.check(lib.shasta_bn_maps_stats_f32(hip.ptr(dst), B, C, plane, total, off, hip.ptr(mm), hip.ptr(ws), ws.numel(), stream),
+                          "shasta_bn_maps_stats_f32")
+                self._stale.add(i)  # (before the launch that writes the running statistics)
+                hip.check(lib.shasta_bn_maps_finalize_f32(hip.ptr(mm), C, float(B * plane), float(bn.eps), float(bn.momentum), hip.ptr(stat),
+                                                          hip.ptr(bn.running_mean), hip.ptr(bn.running_var),
+                                                          ctypes.c_void_p(bn.num_batches_tracked.data_ptr()), stream),
+                          "shasta_bn_maps_finalize_f32")
+                hip.check(lib.shasta_bn_maps_apply_f32(hip.ptr(dst), B, C, plane, total, off, hip.ptr(stat), hip.ptr(bn.weight.detach()),
+                                                       hip.ptr(bn.bias.detach()), 1, stream), "shasta_bn_maps_apply_f32")
+            else:
+                hip.check(lib.shasta_neck_layer_f32(*args), "shasta_neck_layer_f32")
             if role == "block":
                 cur, nxt = dst, nxt ^ 1
         return out
