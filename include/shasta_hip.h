@@ -863,6 +863,62 @@ int shasta_adam_lowrank_dx_f32(float* param, float* exp_avg, float* exp_avg_sq, 
                                size_t workspace_bytes, double lr, double beta1, double beta2, float eps, float weight_decay, int step,
                                const float* d_dyn, shasta_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Multi-sweep cloud assembly (csrc/sweeps.hip): raw sweep rows -> the reader's input, bit-identical to
+ * det3d/datasets/pipelines/loading.py:45-69,111-148 (LoadPointCloudFromFile: read_file, remove_close, read_sweep, concatenate) and,
+ * optionally, the point half of det3d/datasets/pipelines/preprocess.py:126-136 (flip, rotate, scale, translate).
+ *  raw        (total_rows, raw_ndim) fp32: the rows of all segments back to back, in segment order.  3 <= raw_ndim <= 8.
+ *  h_segments HOST array of num_segments (<= 1024) entries, read before the call returns (a pinned array is copied without
+ *             a wait).  Segment = one file: `rows` rows that belong to cloud `cloud` (0 .. num_clouds - 1, never decreasing along the
+ *             array; num_clouds <= 32; a cloud may have no segment); sum of rows == total_rows.
+ *             SHASTA_SWEEP_DROP_CLOSE: a row is dropped iff fabs((double)x) < radius && fabs((double)y) < radius (strict; a NaN stays).
+ *             SHASTA_SWEEP_TRANSFORM : r_i = ((m[i][0] x + m[i][1] y) + m[i][2] z) + m[i][3], i = 0..2, m = transform (3 x 4, row-major):
+ *                                      float64 products of the fp32 coordinates, each rounded, added left to right, no fused
+ *                                      multiply-add, the sum rounded once to fp32.  Without the flag x, y, z are copied bit for bit.
+ *             Columns 3 .. keep - 1 are copied; column `keep` is (float)time_lag.
+ *  h_augment  NULL, or a HOST array of num_clouds entries, applied to every written row of the cloud in this order:
+ *             x, y sign flips (SHASTA_AUG_NEG_Y, then SHASTA_AUG_NEG_X); rotation about z in fp32, x' = fl(fl(x c) + fl(y s)),
+ *             y' = fl(fl(x (-s)) + fl(y c)), z unchanged; scale: fl32((double)v * scale) for v = x, y, z (pass a scale that is an fp32
+ *             value for an fp32 multiply); with SHASTA_AUG_TRANSLATE fl32((double)v + translate[j]).
+ *  out        (capacity, keep + 1) fp32, 1 <= keep <= raw_ndim, capacity >= total_rows.  The surviving rows of every cloud back to back,
+ *             in segment order and in their original order inside a segment.  Rows at and beyond prefix[num_clouds] are not written.
+ *  prefix     (num_clouds + 1,) int32 ON THE DEVICE: rows before each cloud, the last word is the number of rows written.
+ *  workspace  shasta_sweeps_workspace_bytes(num_segments, total_rows) bytes (0 for sizes that are not served), 16-byte aligned.
+ * Chain: copy of the tables -> plan (one workgroup) -> count per block of SHASTA_SWEEPS_BLOCK_ROWS rows (no block spans two segments) ->
+ * one scan of the block counts, which also writes prefix -> write (keep flags recomputed, wave ballot + block offset, rows staged in LDS
+ * and stored as contiguous words).  Integer arithmetic only decides a row's place: the same input gives the same bits on every run.
+ * Refused before any launch: null pointers, sizes out of range, decreasing cloud indices, rows that do not sum to total_rows
+ * (SHASTA_E_ARG); raw_ndim outside 3..8 (SHASTA_E_UNSUPPORTED); a workspace not 16-byte aligned (SHASTA_E_ALIGN) or short
+ * (SHASTA_E_WORKSPACE).
+ * ------------------------------------------------------------------------------------------ */
+#define SHASTA_SWEEPS_BLOCK_ROWS 256
+#define SHASTA_SWEEPS_MAX_CLOUDS 32
+#define SHASTA_SWEEPS_MAX_SEGMENTS 1024
+#define SHASTA_SWEEP_TRANSFORM 1
+#define SHASTA_SWEEP_DROP_CLOSE 2
+typedef struct shasta_sweep_segment {
+    int32_t rows;
+    int32_t cloud;
+    int32_t flags; /* SHASTA_SWEEP_* */
+    int32_t reserved;
+    double transform[12];
+    double time_lag;
+} shasta_sweep_segment; /* 120 bytes */
+#define SHASTA_AUG_NEG_Y 1
+#define SHASTA_AUG_NEG_X 2
+#define SHASTA_AUG_TRANSLATE 4
+typedef struct shasta_sweep_augment {
+    int32_t flags; /* SHASTA_AUG_* */
+    float c, s;    /* cos and sin of the rotation angle, rounded to fp32 by the caller */
+    int32_t reserved;
+    double scale;
+    double translate[3];
+} shasta_sweep_augment; /* 48 bytes */
+size_t shasta_sweeps_workspace_bytes(int num_segments, long total_rows);
+int shasta_sweeps_assemble_f32(const float* raw, long total_rows, int raw_ndim, const shasta_sweep_segment* h_segments, int num_segments,
+                               int num_clouds, int keep, double radius, const shasta_sweep_augment* h_augment, float* out, long capacity,
+                               int32_t* prefix, void* workspace, size_t workspace_bytes, shasta_stream_t stream);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus

@@ -113,6 +113,7 @@ class BEVMap(SingleStageBEV):
 
 class CloudMaps:
     """Neck outputs of frames from their point clouds: `clouds(token)` -> (P, ndim) fp32 array or tensor, `model` a BEVMap in eval mode.
+    A `clouds` object with a `batch(tokens, device)` method (sweeps.SweepClouds) is asked for a whole group's device tensors at once.
     `neck_batch(tokens, device)` -> (n, C, H, W) fp32, the tokens run through the model in groups of at most `max_clouds`."""
 
     def __init__(self, model, clouds, max_clouds=8):
@@ -132,6 +133,7 @@ class CloudMaps:
         outs = []
         with torch.no_grad():
             for i in range(0, len(tokens), self.max_clouds):
-                pts = [self._cloud(t, device) for t in tokens[i:i + self.max_clouds]]
+                group = tokens[i:i + self.max_clouds]
+                pts = list(self.clouds.batch(group, device)) if hasattr(self.clouds, "batch") else [self._cloud(t, device) for t in group]
                 outs.append(self.model(dict(points=pts)))
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)

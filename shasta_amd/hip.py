@@ -58,6 +58,8 @@ SYMBOLS = {
     "shasta_voxelize_mean_batch_f32": (_I, [_P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "shasta_dynvox_workspace_bytes": (_Z, [_P, _I, _I, _I, _I]),
     "shasta_dynvox_mean_f32": (_I, [_P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _Z, _P]),
+    "shasta_sweeps_workspace_bytes": (_Z, [_I, C.c_long]),
+    "shasta_sweeps_assemble_f32": (_I, [_P, C.c_long, _I, _P, _I, _I, _I, C.c_double, _P, _P, C.c_long, _P, _P, _Z, _P]),
     "shasta_voxel_mean_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "shasta_bev_gather_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _P, _I, _I, _P]),
     "shasta_shared_conv_packed_bytes": (_Z, [_I]),

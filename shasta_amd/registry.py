@@ -62,3 +62,4 @@ def build_from_cfg(cfg, registry, default_args=None):
 
 
 READERS, BACKBONES, NECKS, TRACK, SECOND_STAGE, BEV = (Registry(n) for n in ("reader", "backbone", "neck", "track", "second_stage", "bev"))
+PIPELINES = Registry("pipeline")  # det3d/datasets/registry.py: the dataset pipeline steps (shasta_amd/sweeps.py)
