@@ -290,7 +290,7 @@ int shasta_spconv_dense_f32(const float* features, const int* coords, int n, int
  *   3. shasta_bn_rows_finalize_f32: stat[0:C] = mean, [C:2C] = 1 / sqrt(M2 / n + eps); running statistics (NULL to skip) updated as
  *      nn.BatchNorm1d does: (1 - momentum) r + momentum new with the unbiased variance M2 / (n - 1), the blend evaluated in float64 and
  *      rounded once; *num_batches_tracked += 1.  n is an argument of its own (as in shasta_bn_finalize_f32): a synchronised BatchNorm
- *      can merge (mean, M2, n) over the ranks between steps 2 and 3.
+ *      merges (mean, M2, n) over the ranks between steps 2 and 3 (shasta_bn_sync_finalize_f32 below takes this step's place).
  *   4. shasta_bn_rows_apply_f32: out = relu?( ((y - mean) invstd) gamma + beta + residual? ), residual (n, C) or NULL.  y, residual and
  *      out 16-byte aligned; out may alias y or residual (an element is read and written by the same thread); a NaN stays a NaN through
  *      the ReLU; rows >= n are not written.
@@ -325,7 +325,8 @@ int shasta_bn_rows_apply_f32(const float* y, long n, int C, const float* stat, c
  *   3. shasta_bn_maps_finalize_f32: the semantics of shasta_bn_rows_finalize_f32 (one shared device routine): stat[0:C] = mean,
  *      [C:2C] = 1 / sqrt(M2 / n + eps); running statistics (NULL to skip) updated as nn.BatchNorm2d does: (1 - momentum) r + momentum new
  *      with the unbiased variance M2 / (n - 1), the blend evaluated in float64 and rounded once; *num_batches_tracked += 1.  n is an
- *      argument of its own: a synchronised BatchNorm can merge (mean, M2, n) over the ranks between steps 2 and 3.
+ *      argument of its own: a synchronised BatchNorm merges (mean, M2, n) over the ranks between steps 2 and 3
+ *      (shasta_bn_sync_finalize_f32 below takes this step's place).
  *   4. shasta_bn_maps_apply_f32: in place on the slice, y = relu?( ((y - mean) invstd) gamma + beta ) - the order of operations of
  *      shasta_bn_rows_apply_f32; a NaN stays a NaN through the ReLU.
  * Every refusal (null pointer, a slice that leaves the tensor, the grid limit, SHASTA_E_UNSUPPORTED for other widths, a short
@@ -341,6 +342,31 @@ int shasta_bn_maps_finalize_f32(const float* mean_m2, int C, double n, float eps
                                 float* running_var, long* num_batches_tracked, shasta_stream_t stream);
 int shasta_bn_maps_apply_f32(float* y, int B, int C, long plane, int channels_total, int channel_offset, const float* stat,
                              const float* gamma, const float* beta, int relu, shasta_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Batch statistics synchronised over ranks (csrc/bn_sync.hip): step 3 of the two sections above for a batch that is spread over R
+ * processes, as the reference trains (apex.parallel.convert_syncbn_model + DDP, tools/nusc_shasta/train.py:155-156: every BatchNorm of
+ * the frozen backbone and neck normalises with the GLOBAL batch).  A RECORD is one rank's statistics of one BatchNorm call: 2 C floats,
+ * mean[0:C] then M2[C:2C] - exactly what shasta_bn_rows_stats_f32 / shasta_bn_maps_stats_f32 write to mean_m2, so step 2 writes
+ * straight into the front of the local record - followed by the rank's value count as one int64 at byte offset 8 C.  A record is
+ * shasta_bn_sync_record_bytes(C) = 8 C + 8 bytes (0 for a C that is not served) and 8-byte aligned; `records` holds R of them in rank
+ * order (an all-gather of the local record).
+ * shasta_bn_sync_finalize_f32: one thread per channel, float64.  Records are merged sequentially in rank order with Chan's update
+ * (d = mean_r - mean; N' = N + n_r; mean += d n_r / N'; M2 += M2_r + d d N n_r / N'), starting from the first non-empty record as it
+ * is; records of count 0 are skipped.  Merged mean and M2 are rounded once to fp32 (written to mean_m2, NULL to skip; the total count to
+ * *n_total, device memory, NULL to skip), then the shared finalize routine runs with n = N: stat[0:C] = mean, [C:2C] = 1 / sqrt(M2 / N
+ * + eps), running statistics (NULL to skip) blended in float64 with the unbiased variance M2 / (N - 1) and rounded once,
+ * *num_batches_tracked += 1.  For R = 1 the merge is the identity: the same bits as shasta_bn_rows_finalize_f32 /
+ * shasta_bn_maps_finalize_f32 on the same mean_m2 and n.  Every rank computes from the same bytes in the same order: bit-equal results
+ * on all ranks.  Counts are int64 and merge exactly beyond 2^24.  A total count of 0 or any negative count is a contract violation:
+ * stat (and mean_m2) become NaN, *n_total = 0, the running statistics and *num_batches_tracked stay untouched - no fault, no host read.
+ * Served: C a multiple of 16, 16 <= C <= 1024; 1 <= R <= 64; anything else is SHASTA_E_UNSUPPORTED.  NULL records or stat is
+ * SHASTA_E_ARG; records, n_total, num_batches_tracked not 8-byte aligned SHASTA_E_ALIGN.  Every refusal is made before any launch; the
+ * launcher allocates nothing and does not synchronise (capturable).
+ * ------------------------------------------------------------------------------------------ */
+size_t shasta_bn_sync_record_bytes(int C);
+int shasta_bn_sync_finalize_f32(const void* records, int R, int C, float eps, float momentum, float* stat, float* mean_m2, long* n_total,
+                                float* running_mean, float* running_var, long* num_batches_tracked, shasta_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * K0 in train() mode (csrc/shared_conv_train.hip): what autograd does for `self.shared_conv(bev_map)` when the reference trains it -

@@ -27,6 +27,15 @@ eval() is not affected by the switch.  A level with fewer than 2 rows raises Val
 `ShastaHipError`.  Levels, row orders and host synchronisations are the eval forward's.  There is no backward: the parameters stay
 frozen (`requires_grad_(False)`) or the call runs under `torch.no_grad()`.
 
+SYNCHRONISED STATISTICS: after `sync_bn.convert_syncbn_model(model)` (the reference's training run, tools/nusc_shasta/train.py:155-156)
+every norm is a `sync_bn.SyncBatchNorm`.  With more than one rank in its process group, a layer on batch statistics normalises with the
+statistics of ALL ranks' rows: stats kernel into the local record, one all-gather, `shasta_bn_sync_finalize_f32` (csrc/bn_sync.hip, the
+merge on the device, no host read), apply - `sync_bn.RankStats`.  The running statistics are bit-equal on all ranks.  The "more than 1
+value" refusal becomes a refusal of an empty local input, made before the first collective (a non-empty cloud has at least one row at
+every level, and two ranks then have at least two).  The set of layers on batch statistics must be the same on every rank (the
+reference's frozen set-up guarantees it); a rank that raises before a collective leaves the others to torch.distributed's timeout, as
+with any collective.  World 1, or no initialised process group: the calls and the bits of the plain BatchNorm1d.
+
 Registration: the class is NOT put into BACKBONES at import (a string config `type="SpMiddleResNetFHD"` stays a KeyError until the
 user decides).  Either pass the class itself, `backbone=dict(type=shasta_amd.backbone.SpMiddleResNetFHD, num_input_features=5,
 ds_factor=8)`, or call `shasta_amd.backbone.register()` once and keep the reference's string configs.
@@ -38,7 +47,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import hip
+from . import hip, sync_bn
 from .neck import build_norm_layer
 from .registry import BACKBONES
 
@@ -241,9 +250,9 @@ class SpMiddleResNetFHD(nn.Module):
             raise hip.ShastaHipError("SpMiddleResNetFHD: fp32 voxel features only, got %s" % voxel_features.dtype)
         params = []
         for conv, bn in self._pairs():
-            if not (isinstance(bn, nn.BatchNorm1d) and bn.affine and bn.track_running_stats):
-                raise hip.ShastaHipError("SpMiddleResNetFHD: only BatchNorm1d with affine parameters and running statistics is served, got %s"
-                                         % type(bn).__name__)
+            if not (isinstance(bn, (nn.BatchNorm1d, sync_bn.SyncBatchNorm)) and bn.affine and bn.track_running_stats):
+                raise hip.ShastaHipError("SpMiddleResNetFHD: only BatchNorm1d (or its sync_bn.SyncBatchNorm conversion) with affine parameters "
+                                         "and running statistics is served, got %s" % type(bn).__name__)
             if self.training and bn.training and bn.momentum is None:
                 raise hip.ShastaHipError("SpMiddleResNetFHD: BatchNorm1d(momentum=None) (cumulative averaging of the running statistics) "
                                          "is not served in train() mode")
@@ -315,7 +324,7 @@ class SpMiddleResNetFHD(nn.Module):
 
     def _check_rows(self, conv, n_out):
         """torch.nn.functional.batch_norm's check for a layer on batch statistics, before any launch of that layer."""
-        if self._batch is not None and id(conv) in self._batch["bn"] and n_out < 2:
+        if self._batch is not None and id(conv) in self._batch["bn"] and id(conv) not in self._batch["synced"] and n_out < 2:
             raise ValueError("Expected more than 1 value per channel when training, got input size %s"
                              % (torch.Size([n_out, conv.out_channels]),))
 
@@ -333,10 +342,17 @@ class SpMiddleResNetFHD(nn.Module):
         hip.check(lib.shasta_spconv_layer_f32(hip.ptr(x), n_in, conv.in_channels, hip.ptr(nbr), n_out, K, hip.ptr(pk), pk.numel(), C, None, 0,
                                               hip.ptr(y), s), "shasta_spconv_layer_f32")
         mm, stat, ws = st["mean_m2"], st["stat"], st["workspace"]
-        hip.check(lib.shasta_bn_rows_stats_f32(hip.ptr(y), n_out, C, hip.ptr(mm), hip.ptr(ws), ws.numel(), s), "shasta_bn_rows_stats_f32")
-        hip.check(lib.shasta_bn_rows_finalize_f32(hip.ptr(mm), C, float(n_out), float(bn.eps), float(bn.momentum), hip.ptr(stat),
-                                                  hip.ptr(bn.running_mean), hip.ptr(bn.running_var),
-                                                  ctypes.c_void_p(bn.num_batches_tracked.data_ptr()), s), "shasta_bn_rows_finalize_f32")
+        world = st["synced"].get(id(conv), 1)
+        if world > 1:  # statistics of all ranks: the stats kernel writes the front of the local record, gather, merged finalize
+            ranks = st["ranks"]
+            hip.check(lib.shasta_bn_rows_stats_f32(hip.ptr(y), n_out, C, hip.ptr(ranks.local(C, world)), hip.ptr(ws), ws.numel(), s),
+                      "shasta_bn_rows_stats_f32")
+            ranks.finalize(bn, C, n_out, stat, s)
+        else:
+            hip.check(lib.shasta_bn_rows_stats_f32(hip.ptr(y), n_out, C, hip.ptr(mm), hip.ptr(ws), ws.numel(), s), "shasta_bn_rows_stats_f32")
+            hip.check(lib.shasta_bn_rows_finalize_f32(hip.ptr(mm), C, float(n_out), float(bn.eps), float(bn.momentum), hip.ptr(stat),
+                                                      hip.ptr(bn.running_mean), hip.ptr(bn.running_var),
+                                                      ctypes.c_void_p(bn.num_batches_tracked.data_ptr()), s), "shasta_bn_rows_finalize_f32")
         st["updated"].append(conv)
         hip.check(lib.shasta_bn_rows_apply_f32(hip.ptr(y), n_out, C, hip.ptr(stat), hip.ptr(bn.weight.detach()), hip.ptr(bn.bias.detach()),
                                                hip.ptr(residual), 1 if relu else 0, hip.ptr(y), s), "shasta_bn_rows_apply_f32")
@@ -393,7 +409,12 @@ class SpMiddleResNetFHD(nn.Module):
         if not batch:
             return self._forward(x, coords, B, grid)
         width = max(bn.num_features for bn in batch.values())
-        self._batch = dict(bn=batch, updated=[], mean_m2=torch.empty(2 * width, dtype=torch.float32, device=dev),
+        # id(conv) -> world of the layers whose SyncBatchNorm shares its statistics with other ranks
+        synced = {k: sync_bn.synced_world(bn) for k, bn in batch.items() if sync_bn.synced_world(bn) > 1}
+        if synced and x.shape[0] == 0:  # (before the first collective; a non-empty cloud has at least 1 row at every level)
+            raise ValueError("SpMiddleResNetFHD: an empty local input cannot take part in synchronised batch statistics")
+        ranks = sync_bn.RankStats(max(batch[k].num_features for k in synced), max(synced.values()), dev) if synced else None
+        self._batch = dict(bn=batch, synced=synced, ranks=ranks, updated=[], mean_m2=torch.empty(2 * width, dtype=torch.float32, device=dev),
                            stat=torch.empty(2 * width, dtype=torch.float32, device=dev),
                            workspace=torch.empty(lib.shasta_bn_rows_workspace_bytes(width), dtype=torch.uint8, device=dev))
         try:

@@ -97,6 +97,8 @@ SYMBOLS = {
     "shasta_bn_maps_stats_f32": (_I, [_P, _I, _I, C.c_long, _I, _I, _P, _P, _Z, _P]),
     "shasta_bn_maps_finalize_f32": (_I, [_P, _I, C.c_double, _F, _F, _P, _P, _P, _P, _P]),
     "shasta_bn_maps_apply_f32": (_I, [_P, _I, _I, C.c_long, _I, _I, _P, _P, _P, _I, _P]),
+    "shasta_bn_sync_record_bytes": (_Z, [_I]),
+    "shasta_bn_sync_finalize_f32": (_I, [_P, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P, _P]),
     "shasta_conv_train_supported": (_I, [_I, _I, _I]),
     "shasta_shared_conv_pack_raw_f32": (_I, [_P, _P, _I, _P, _Z, _P]),
     "shasta_shared_conv_pack_raw_f16x2": (_I, [_P, _P, _I, _P, _Z, _P]),

@@ -25,6 +25,15 @@ without the epilogue's affine and ReLU, reading the weight section of the SAME p
 version counter, so a forward marks the alpha / beta' of the layers it updated as stale and the next eval use re-packs them.  The
 statistics workspace and the `stat` buffers live with the ping-pong buffers: no host synchronisation, no allocation but the result,
 capturable.  `n = B * OH * OW < 2` raises ValueError as torch does; `momentum=None` raises `ShastaHipError`.
+
+SYNCHRONISED STATISTICS: the plan follows the modules (`_plan`), so after `sync_bn.convert_syncbn_model` - the reference's training run,
+tools/nusc_shasta/train.py:155-156 - the layers read the new `SyncBatchNorm` modules and their `training` flags.  A `SyncBatchNorm`
+layer on batch statistics whose process group has more than one rank normalises with the statistics of ALL ranks' maps: the stats
+kernel writes the front of the local record, one all-gather, `shasta_bn_sync_finalize_f32` (csrc/bn_sync.hip: the merge on the device,
+no host read), apply - `sync_bn.RankStats`, kept with the other buffers.  The running statistics are bit-equal on all ranks; the count
+refusal does not apply (every rank has B >= 1).  The set of layers on batch statistics must be the same on every rank (the reference's
+frozen set-up guarantees it); a rank that raises before a collective leaves the others to torch.distributed's timeout, as with any
+collective.  The collective is not capturable in a graph.  World 1, or no initialised process group: the calls and bits of BatchNorm2d.
 """
 import ctypes
 
@@ -32,7 +41,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import hip
+from . import hip, sync_bn
 from .registry import NECKS
 
 C3S1, C3S2, C1, D2 = 0, 1, 2, 3  # include/shasta_hip.h SHASTA_NECK_*
@@ -109,7 +118,9 @@ class RPN(nn.Module):
         self._stale = set()      # layers whose running statistics the kernels wrote: weights packed, alpha / beta' out of date
         self._bufs = None        # the two ping-pong buffers
         self._train_bufs = None  # train() mode: mean_m2, stat, the statistics workspace
-        self._plan = self._make_plan()
+        self._rank_stats = None  # train() mode with a SyncBatchNorm over several ranks: the record and gather buffers (sync_bn.RankStats)
+        self._plan_now = None    # the chain of kernel layers and the module identities it was built from: see `_plan`
+        self._plan_ids = None
 
     def _make_layer(self, inplanes, planes, num_blocks, stride=1):
         layers = [nn.ZeroPad2d(1), nn.Conv2d(inplanes, planes, 3, stride=stride, bias=False),
@@ -144,6 +155,18 @@ class RPN(nn.Module):
         return x
 
     # ---- kernel path ----------------------------------------------------------------------------------------
+    @property
+    def _plan(self):
+        """The plan follows the modules: it is rebuilt - and the packed layers are dropped with it - when the identity of any module
+        under `blocks` / `deblocks` differs from the one it was built from (`sync_bn.convert_syncbn_model` swaps new BatchNorm modules
+        in, which share the old ones' tensors; the old objects' `training` flag no longer follows `train()` / `eval()`)."""
+        ids = tuple(id(m) for seq in (*self.blocks, *self.deblocks) for m in seq)
+        if ids != self._plan_ids:
+            self._plan_now, self._plan_ids = self._make_plan(), ids
+            self._packed = self._packed_key = None
+            self._stale = set()
+        return self._plan_now
+
     def _make_plan(self):
         """The chain of kernel layers: [(kind, conv, bn, role)], role = "block" or the deblock's index; None when a layer is outside what
         shasta_neck_layer_f32 serves (the shapes are checked per call, they depend on H and W)."""
@@ -152,7 +175,7 @@ class RPN(nn.Module):
         plan = []
 
         def bn_ok(bn):
-            return isinstance(bn, nn.BatchNorm2d) and bn.affine and bn.track_running_stats
+            return isinstance(bn, (nn.BatchNorm2d, sync_bn.SyncBatchNorm)) and bn.affine and bn.track_running_stats
 
         for i, block in enumerate(self.blocks):
             mods = list(block)
@@ -201,10 +224,10 @@ class RPN(nn.Module):
         statistics in this forward) reads the weight section only, so alpha / beta' marked stale by an earlier train() forward do not
         make it re-pack; every other layer is re-packed when stale."""
         if self._packed is None or self._packed_key is None:
-            self._packed, self._packed_key, self._stale = [None] * len(self._plan), [None] * len(self._plan), set()
+            self._packed, self._packed_key, self._stale = [None] * len(self._plan_now), [None] * len(self._plan_now), set()
         lib = hip.load()
         packed = self._packed
-        for i, (kind, conv, bn, _) in enumerate(self._plan):
+        for i, (kind, conv, bn, _) in enumerate(self._plan_now):
             key = tuple((t.data_ptr(), t._version) for t in self._tensors(conv, bn)) + (str(dev),)
             if packed[i] is not None and self._packed_key[i] == key and (i in batch or i not in self._stale):
                 continue
@@ -247,13 +270,13 @@ class RPN(nn.Module):
             return frozenset()
         lib = hip.load()
         batch = []
-        for i, ((_, conv, bn, _), s) in enumerate(zip(self._plan, shapes)):
+        for i, ((_, conv, bn, _), s) in enumerate(zip(self._plan_now, shapes)):
             if not bn.training:
                 continue
             if bn.momentum is None:
                 raise hip.ShastaHipError("RPN: BatchNorm2d(momentum=None) (cumulative averaging of the running statistics) is not served "
                                          "in train() mode")
-            if B * s[2] * s[3] < 2:
+            if B * s[2] * s[3] < 2 and sync_bn.synced_world(bn) == 1:  # (several ranks: B >= 1 each, at least 2 values in total)
                 raise ValueError("Expected more than 1 value per channel when training, got input size %s"
                                  % (torch.Size([B, conv.out_channels, s[2], s[3]]),))
             if not lib.shasta_bn_maps_supported(conv.out_channels):
@@ -263,8 +286,8 @@ class RPN(nn.Module):
 
     def _ensure_train_bufs(self, B, shapes, batch, dev):
         lib = hip.load()
-        cmax = max(self._plan[i][1].out_channels for i in batch)
-        need = max(lib.shasta_bn_maps_workspace_bytes(B, self._plan[i][1].out_channels, shapes[i][2] * shapes[i][3]) for i in batch)
+        cmax = max(self._plan_now[i][1].out_channels for i in batch)
+        need = max(lib.shasta_bn_maps_workspace_bytes(B, self._plan_now[i][1].out_channels, shapes[i][2] * shapes[i][3]) for i in batch)
         tb = self._train_bufs
         if tb is None or tb[0].device != dev or tb[0].numel() < 2 * cmax or tb[2].numel() < need:
             self._train_bufs = None
@@ -272,10 +295,17 @@ class RPN(nn.Module):
                                      torch.empty(need, dtype=torch.uint8, device=dev))
         return tb
 
+    def _ensure_rank_stats(self, width, world, dev):
+        rs = self._rank_stats
+        if rs is None or rs.width < width or rs.world < world or rs.device != dev:
+            self._rank_stats = None
+            rs = self._rank_stats = sync_bn.RankStats(width, world, dev)
+        return rs
+
     def _kernel_path(self, x):
         if (self.training and not self.batch_statistics) or self._plan is None or x.dim() != 4 or x.dtype != torch.float32:
             return False
-        params = [t for _, conv, bn, _ in self._plan for t in self._tensors(conv, bn)]
+        params = [t for _, conv, bn, _ in self._plan_now for t in self._tensors(conv, bn)]
         if any(t.dtype != torch.float32 for t in params):
             return False
         if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in params)):
@@ -298,19 +328,22 @@ class RPN(nn.Module):
         batch = self._batch_layers(B, shapes)
         self._ensure_packed(dev, batch)
         x = x.contiguous()
-        need = max([B * conv.out_channels * s[2] * s[3] for (_, conv, _, role), s in zip(self._plan, shapes) if role == "block"])
+        need = max([B * conv.out_channels * s[2] * s[3] for (_, conv, _, role), s in zip(self._plan_now, shapes) if role == "block"])
         if self._bufs is None or self._bufs[0].numel() < need or self._bufs[0].device != dev:
             self._bufs = None
             self._bufs = [torch.empty(need, dtype=torch.float32, device=dev) for _ in range(2)]
         ctot = sum(self._num_upsample_filters)
         offs = np.concatenate([[0], np.cumsum(self._num_upsample_filters)]).tolist()
-        oh, ow = next(s[2:] for (_, _, _, role), s in zip(self._plan, shapes) if role != "block")
+        oh, ow = next(s[2:] for (_, _, _, role), s in zip(self._plan_now, shapes) if role != "block")
         out = torch.empty(B, ctot, oh, ow, dtype=torch.float32, device=dev)
         stream = hip.stream_ptr()
         if batch:
             mm, stat, ws = self._ensure_train_bufs(B, shapes, batch, dev)
+            worlds = {i: sync_bn.synced_world(self._plan_now[i][2]) for i in batch}  # > 1: statistics shared with other ranks
+            if max(worlds.values()) > 1:
+                ranks = self._ensure_rank_stats(max(self._plan_now[i][1].out_channels for i in batch if worlds[i] > 1), max(worlds.values()), dev)
         cur, nxt = x, 0
-        for i, ((kind, conv, bn, role), pk, s) in enumerate(zip(self._plan, self._packed, shapes)):
+        for i, ((kind, conv, bn, role), pk, s) in enumerate(zip(self._plan_now, self._packed, shapes)):
             if role == "block":
                 dst, total, off = self._bufs[nxt], conv.out_channels, 0
             else:
@@ -320,13 +353,18 @@ class RPN(nn.Module):
             if i in batch:  # raw convolution into the destination, batch statistics of it, finalize, apply in place
                 C, plane = conv.out_channels, s[2] * s[3]
                 hip.check(lib.shasta_neck_layer_raw_f32(*args), "shasta_neck_layer_raw_f32")
-                hip.check(lib.shasta_bn_maps_stats_f32(hip.ptr(dst), B, C, plane, total, off, hip.ptr(mm), hip.ptr(ws), ws.numel(), stream),
+                world = worlds[i]
+                local = ranks.local(C, world) if world > 1 else mm  # (several ranks: the front of the local record)
+                hip.check(lib.shasta_bn_maps_stats_f32(hip.ptr(dst), B, C, plane, total, off, hip.ptr(local), hip.ptr(ws), ws.numel(), stream),
                           "shasta_bn_maps_stats_f32")
                 self._stale.add(i)  # (before the launch that writes the running statistics)
-                hip.check(lib.shasta_bn_maps_finalize_f32(hip.ptr(mm), C, float(B * plane), float(bn.eps), float(bn.momentum), hip.ptr(stat),
-                                                          hip.ptr(bn.running_mean), hip.ptr(bn.running_var),
-                                                          ctypes.c_void_p(bn.num_batches_tracked.data_ptr()), stream),
-                          "shasta_bn_maps_finalize_f32")
+                if world > 1:  # one all-gather of the record, the merged finalize on the device
+                    ranks.finalize(bn, C, B * plane, stat, stream)
+                else:
+                    hip.check(lib.shasta_bn_maps_finalize_f32(hip.ptr(mm), C, float(B * plane), float(bn.eps), float(bn.momentum), hip.ptr(stat),
+                                                              hip.ptr(bn.running_mean), hip.ptr(bn.running_var),
+                                                              ctypes.c_void_p(bn.num_batches_tracked.data_ptr()), stream),
+                              "shasta_bn_maps_finalize_f32")
                 hip.check(lib.shasta_bn_maps_apply_f32(hip.ptr(dst), B, C, plane, total, off, hip.ptr(stat), hip.ptr(bn.weight.detach()),
                                                        hip.ptr(bn.bias.detach()), 1, stream), "shasta_bn_maps_apply_f32")
             else:

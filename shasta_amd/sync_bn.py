@@ -8,7 +8,13 @@ each rank's [mean, sum of squared deviations, count] per channel (one small coll
 partial variances are merged (no E[x^2] - mean^2 cancellation), backward all-reduces [sum dy, sum dy*xhat].
 Counts are exchanged, so ranks may hold different numbers of pixels.  Same parameter / buffer names as nn.BatchNorm2d
 (`weight, bias, running_mean, running_var, num_batches_tracked`): state_dict keys are unchanged.  The structure follows the
-all-gather / all-reduce pairing of the reference's own NaiveSyncBatchNorm (det3d/models/utils/norm.py:9-56)."""
+all-gather / all-reduce pairing of the reference's own NaiveSyncBatchNorm (det3d/models/utils/norm.py:9-56).
+
+The conversion reaches every BatchNorm of the model, the frozen backbone's BatchNorm1d and the frozen neck's BatchNorm2d included; their
+kernel paths (backbone.py, neck.py with `batch_statistics=True`) do not call `SyncBatchNorm.forward` but share `RankStats` below: the
+stats kernels' (mean, M2) and the count all-gathered as one record, merged on the device by csrc/bn_sync.hip with no host read."""
+import ctypes
+
 import torch
 import torch.distributed as dist
 import torch.nn as nn
@@ -102,6 +108,69 @@ class SyncBatchNorm(nn.modules.batchnorm._BatchNorm):
 
 class SyncBatchNorm2d(SyncBatchNorm):
     """The 4-D case (`shared_conv.1`); kept as its own name for checkpoints / configs that refer to it."""
+
+
+def synced_world(bn):
+    """Number of ranks whose batch statistics `bn` shares on the kernel paths of the frozen stages: > 1 for a `SyncBatchNorm` whose process
+    group is initialised with more than one rank, else 1 (a plain BatchNorm, world 1, torch.distributed not initialised)."""
+    return _world(bn.process_group) if isinstance(bn, SyncBatchNorm) else 1
+
+
+class RankStats:
+    """The piece the frozen backbone (backbone.py) and neck (neck.py) share for a `SyncBatchNorm` layer on batch statistics with more than
+    one rank: the local RECORD of csrc/bn_sync.hip (mean | M2 as the stats kernels write them, then the value count as an int64), one
+    `dist.all_gather` of it over `bn.process_group`, one `shasta_bn_sync_finalize_f32` on the caller's stream.  No host read: the count is
+    written by `fill_` on an int64 view of the record's tail, the merge runs on the device in float64, sequentially in rank order, on the
+    same gathered bytes on every rank - `stat` and the running statistics are bit-equal across ranks.
+
+    One object per forward, sized for the widest layer and reused by every layer (a layer of C channels takes the front 8 C + 8 bytes of
+    the record and the front R (8 C + 8) bytes of the gather buffer).  The reuse is safe under stream ordering: the stats kernel that
+    writes the record, the collective and the finalize that reads the gathered records are all ordered on the caller's stream - the
+    blocking collective makes the current stream wait for it, and starts only after the work queued on that stream before it - so the
+    next layer's stats kernel cannot overwrite a record that is still being sent, and the next collective cannot overwrite records the
+    previous finalize still reads.
+
+    Every rank must make the same calls in the same order: the set of layers on batch statistics must be the same on all ranks (the
+    reference's frozen set-up guarantees it).  A rank that raises before a collective leaves the others to torch.distributed's timeout."""
+
+    def __init__(self, width, world, device):
+        from . import hip
+        self._hip = hip
+        self.width, self.world, self.device = int(width), int(world), device
+        nbytes = hip.load().shasta_bn_sync_record_bytes(self.width)
+        if nbytes == 0:
+            raise hip.ShastaHipError("synchronised batch statistics over %d channels are not served" % self.width)
+        self._record = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        self._gathered = torch.empty(nbytes * self.world, dtype=torch.uint8, device=device)
+        self._views = {}
+
+    def _view(self, C, world):
+        v = self._views.get((C, world))
+        if v is None:
+            nbytes = self._hip.load().shasta_bn_sync_record_bytes(C)
+            if nbytes == 0 or C > self.width or world > self.world:
+                raise self._hip.ShastaHipError("synchronised batch statistics over %d channels on %d ranks are not served" % (C, world))
+            rec = self._record[:nbytes]
+            gathered = self._gathered[:nbytes * world]
+            v = self._views[(C, world)] = (rec, rec[:8 * C].view(torch.float32), rec[8 * C:].view(torch.int64), gathered,
+                                           list(gathered.view(world, nbytes).unbind(0)))
+        return v
+
+    def local(self, C, world):
+        """fp32 view (2 C) of the local record's front: the `mean_m2` argument of the stats kernel."""
+        return self._view(C, world)[1]
+
+    def finalize(self, bn, C, count, stat, stream):
+        """count -> record tail, all-gather over bn.process_group, merged finalize into `stat` and the module's running statistics."""
+        hip = self._hip
+        world = _world(bn.process_group)
+        rec, _, tail, gathered, parts = self._view(C, world)
+        tail.fill_(int(count))
+        dist.all_gather(parts, rec, group=bn.process_group)
+        hip.check(hip.load().shasta_bn_sync_finalize_f32(hip.ptr(gathered), world, C, float(bn.eps), float(bn.momentum), hip.ptr(stat), None, None,
+                                                         hip.ptr(bn.running_mean), hip.ptr(bn.running_var),
+                                                         ctypes.c_void_p(bn.num_batches_tracked.data_ptr()), stream),
+                  "shasta_bn_sync_finalize_f32")
 
 
 def convert_syncbn_model(module, process_group=None):

@@ -8,6 +8,12 @@ BatchNorm1d on batch statistics, csrc/bn_rows.hip): the convolutions then write 
 level are listed next to them.
 
     python tools/time_backbone.py [--batches 1 2] [--iters 5] [--points 300000] [--train]
+
+With --sync-ranks N the train()-mode forward runs on N GPUs, one fresh process each with its own clouds, the module converted with
+sync_bn.convert_syncbn_model (batch statistics of all ranks over RCCL: one small all-gather and csrc/bn_sync.hip per layer); per rank
+the synced forward beside the un-synced one of the same weights.  Fewer GPUs than ranks: "not measured".
+
+    python tools/time_backbone.py --sync-ranks 4 [--batches 1 2] [--iters 5] [--points 300000]
 """
 import argparse
 import json
@@ -20,6 +26,7 @@ import torch
 sys.path.insert(0, os.getcwd())
 from shasta_amd import backbone, hip  # noqa: E402
 from shasta_amd.voxel_generator import VoxelGenerator  # noqa: E402
+from tools import sync_ranks  # noqa: E402
 
 F32_MATRIX_PEAK = 155e12  # FLOP/s, v_mfma_f32_*_f32 measured
 HBM_RATE = 6.29e12        # B/s, measured float4 copy
@@ -75,13 +82,45 @@ def per_level(calls):
     return levels, dense
 
 
+def sync_child(a):
+    """One rank of --sync-ranks: the un-synced train() forward, then the same weights converted and synced over the ranks."""
+    import copy
+    from shasta_amd.sync_bn import convert_syncbn_model
+    dev = sync_ranks.child(a)
+    torch.manual_seed(0)
+    plain = backbone.SpMiddleResNetFHD(num_input_features=5, ds_factor=8, batch_statistics=True).train().to(dev)
+    synced = convert_syncbn_model(copy.deepcopy(plain)).train()
+    vg = VoxelGenerator([0.075, 0.075, 0.2], [-54, -54, -5, 54, 54, 3], 10, max_voxels=160000)
+    shape = vg.grid_size.tolist()
+    rng = np.random.default_rng(a.sync_rank)  # (every rank its own clouds)
+    res = dict(tool="time_backbone", mode="train, synced", ranks=a.sync_ranks, rank=a.sync_rank, points_per_cloud=a.points,
+               device=torch.cuda.get_device_name(dev), batches=[])
+    with torch.no_grad():
+        for B in a.batches:
+            clouds = [cloud(rng, a.points).to(dev) for _ in range(B)]
+            _, coors, _, mean, nv = vg.generate_batch_device(clouds)
+            nv = nv.cpu().tolist()
+            feats = torch.cat([mean[b, :nv[b]] for b in range(B)]).contiguous()
+            coords = torch.cat([torch.cat([torch.full((nv[b], 1), b, dtype=torch.int32, device=dev), coors[b, :nv[b]]], 1) for b in range(B)])
+            t_plain = sync_ranks.timed_ms(lambda: plain(feats, coords, B, shape), a.iters)
+            t_sync = sync_ranks.timed_ms(lambda: synced(feats, coords, B, shape), a.iters)
+            res["batches"].append(dict(B_per_rank=B, voxels=sum(nv), forward_ms=round(t_plain, 3), forward_synced_ms=round(t_sync, 3)))
+    print(json.dumps(res), flush=True)
+    torch.distributed.destroy_process_group()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 2])
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--points", type=int, default=300000)
     ap.add_argument("--train", action="store_true", help="time the train()-mode forward (batch-statistics BatchNorm1d)")
+    sync_ranks.add_arguments(ap)
     a = ap.parse_args()
+    if a.sync_rank is not None:
+        return sync_child(a)
+    if a.sync_ranks:
+        sys.exit(sync_ranks.parent("time_backbone", a))
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     m = backbone.SpMiddleResNetFHD(num_input_features=5, ds_factor=8, batch_statistics=a.train).train(a.train).to(dev)

@@ -11,6 +11,12 @@ every C call of the train()-mode forward, summed per pass, and the counted traff
 (the statistics read y, the apply reads and writes it) at the measured HBM rate.
 
     python tools/time_neck.py --train [--batches 1 8] [--iters 10] [--hw 180]
+
+With --sync-ranks N the train()-mode forward runs on N GPUs, one fresh process each, the module converted with
+sync_bn.convert_syncbn_model (batch statistics of all ranks over RCCL: one small all-gather and csrc/bn_sync.hip per layer); per rank
+the synced forward beside the un-synced one of the same weights.  Fewer GPUs than ranks: "not measured".
+
+    python tools/time_neck.py --sync-ranks 4 [--batches 1 8] [--iters 10] [--hw 180]
 """
 import argparse
 import json
@@ -22,6 +28,7 @@ import torch
 sys.path.insert(0, os.getcwd())
 import shasta_amd  # noqa: E402
 from shasta_amd import hip, neck  # noqa: E402
+from tools import sync_ranks  # noqa: E402
 
 SHIPPED = dict(layer_nums=[5, 5], ds_layer_strides=[1, 2], ds_num_filters=[128, 256], us_layer_strides=[1, 2], us_num_filters=[256, 256],
                num_input_features=256)
@@ -111,6 +118,26 @@ def train_main(a):
     print(json.dumps(res))
 
 
+def sync_child(a):
+    """One rank of --sync-ranks: the un-synced train() forward, then the same weights converted and synced over the ranks."""
+    import copy
+    from shasta_amd.sync_bn import convert_syncbn_model
+    dev = sync_ranks.child(a)
+    torch.manual_seed(0)
+    plain = shasta_amd.builder.build_neck(dict(type="RPN", batch_statistics=True, **SHIPPED)).train().to(dev)
+    synced = convert_syncbn_model(copy.deepcopy(plain)).train()
+    res = dict(tool="time_neck", mode="train, synced", ranks=a.sync_ranks, rank=a.sync_rank, hw=a.hw, device=torch.cuda.get_device_name(dev),
+               batches=[])
+    with torch.no_grad():
+        for B in a.batches or [1, 8]:
+            x = torch.randn(B, 256, a.hw, a.hw, device=dev) + 0.2
+            t_plain = sync_ranks.timed_ms(lambda: plain(x), a.iters)
+            t_sync = sync_ranks.timed_ms(lambda: synced(x), a.iters)
+            res["batches"].append(dict(B_per_rank=B, hip_train_ms=round(t_plain, 3), hip_train_synced_ms=round(t_sync, 3)))
+    print(json.dumps(res), flush=True)
+    torch.distributed.destroy_process_group()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=None)
@@ -118,7 +145,12 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--hw", type=int, default=180)
     ap.add_argument("--no-layers", action="store_true", help="skip the per-layer timing")
+    sync_ranks.add_arguments(ap)
     a = ap.parse_args()
+    if a.sync_rank is not None:
+        return sync_child(a)
+    if a.sync_ranks:
+        sys.exit(sync_ranks.parent("time_neck", a))
     if a.train:
         return train_main(a)
     a.batches = a.batches or [1, 2, 8]
