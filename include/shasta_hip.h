@@ -680,6 +680,58 @@ int shasta_nms_normal_f32(const float* boxes_sorted, int num_boxes, float thresh
 int shasta_boxes_bev_f32(const float* boxes_a, int num_a, const float* boxes_b, int num_b, int mode, float* out,
                          shasta_stream_t stream);
 
+/* shasta_nms_rotated_f32 over `segments` segments of ONE sorted box array in one call (the same two kernels, the segment as a grid
+ * dimension): segment s is rows [offsets[s], offsets[s + 1]) of boxes_sorted, sorted by descending score inside the segment;
+ * offsets (segments + 1,) int32 on the DEVICE (no count returns to the host).  A segment longer than max_boxes is cut to its first
+ * max_boxes rows (the reference's pre-NMS cut); max_boxes <= 32768, segments <= 65535.
+ *  keep (segments, max_boxes) int32: row s holds the kept boxes' indices INSIDE segment s in score order; num_keep (segments,) int32
+ *  workspace: shasta_nms_batch_workspace_bytes(segments, max_boxes)
+ * Keep lists and counts are those of one shasta_nms_rotated_f32 call per segment, bit for bit. */
+size_t shasta_nms_batch_workspace_bytes(int segments, int max_boxes);
+int shasta_nms_rotated_batch_f32(const float* boxes_sorted, const int32_t* offsets, int segments, int max_boxes, float thresh,
+                                 void* workspace, size_t workspace_bytes, int32_t* keep, int32_t* num_keep, shasta_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The CenterPoint detection head behind the neck map (csrc/head.hip; CenterHead / SepHead / predict of CenterPoint's nuScenes voxel
+ * configuration, shasta_amd/head.py).  Strict fp32, no atomics: the same bits on every run.  Every refusal is made before any launch.
+ *
+ * The head's Conv2d(3, padding 1, bias) -> BatchNorm2d (eval) -> ReLU layers are SHASTA_NECK_C3S1 layers: pack them with
+ * shasta_neck_layer_pack_f32, handing it bn_mean - conv_bias for bn_mean ((acc + b - mean) alpha + beta = acc alpha + beta -
+ * (mean - b) alpha), and run them with shasta_neck_layer_f32; the first convolutions of all heads of a task run as ONE layer with
+ * Cout = 64 x heads (weights and BatchNorm tensors concatenated in head order) into one (B, 64 heads, H, W) tensor.
+ *
+ * shasta_head_final_f32: the heads' last convolutions.  Head h reads channels [64 h, 64 h + 64) of x (B, 64 heads, H, W) and writes
+ * widths[h] (1 .. 3) channels of out (B, C_task = sum of widths, H, W), in head order: 3x3, padding 1, + bias, no norm, no ReLU.
+ *  widths : HOST array of `heads` ints, heads <= SHASTA_HEAD_MAX_HEADS
+ *  packed : shasta_head_final_packed_bytes(heads) bytes written by the caller, per head 2308 floats: [cc = 16][tap = 9][kq = 4][i = 4]
+ *           = weight[i][4 cc + kq][tap / 3][tap % 3] (zero for i >= widths[h]), then bias[4] (zero for i >= widths[h])
+ * shasta_head_supported: 1 when the kernels serve a head of this shape: in_channels % 8 == 0, share_conv_channel % 32 == 0, 1 .. 16
+ *  heads of width 64, final widths 1 .. 3, H, W >= 1, every image below 2^31 elements.
+ *
+ * shasta_head_decode_f32: one task's raw maps (B, C, H, W) -> per image the candidates in ascending pixel order p = iy W + ix.
+ *  score = max_c sigmoid(hm_c), label = the first arg-max; box = [x, y, z, exp(dim0), exp(dim1), exp(dim2), vel0, vel1,
+ *  atan2(rot0, rot1)], x = ((ix + reg0) * out_size_factor) * voxel_x + pc_x (fp32, separately rounded), y likewise with iy, reg1,
+ *  z = height.  A pixel is a candidate iff score > score_threshold and range[0:3] <= (x, y, z) <= range[3:6] (both ends inclusive).
+ *  cfg    : HOST struct; reg .. hm = first channel of each head in the tensor
+ *  box (B, cap, 9) fp32, score (B, cap) fp32, label (B, cap) int32, pixel (B, cap) int32: rows [0, min(count[b], cap)) of image b are
+ *  written and no other; count (B,) int32 on the device = all candidates, also those beyond cap.
+ *  workspace: shasta_head_decode_workspace_bytes(B, H, W).  Block counts, one scan per image, wave ballots: no atomics.
+ * ------------------------------------------------------------------------------------------ */
+#define SHASTA_HEAD_MAX_HEADS 16
+typedef struct shasta_head_decode_cfg {
+    int reg, height, dim, rot, vel, hm, num_class;
+    float out_size_factor, voxel_x, voxel_y, pc_x, pc_y, score_threshold;
+    float range[6];
+} shasta_head_decode_cfg;
+int shasta_head_supported(int in_channels, int share_conv_channel, int heads, const int* widths, int H, int W);
+size_t shasta_head_final_packed_bytes(int heads);
+int shasta_head_final_f32(const float* x, int B, int heads, const int* widths, int H, int W, const void* packed, size_t packed_bytes,
+                          float* out, shasta_stream_t stream);
+size_t shasta_head_decode_workspace_bytes(int B, int H, int W);
+int shasta_head_decode_f32(const float* raw, int B, int C, int H, int W, const shasta_head_decode_cfg* cfg, int cap, float* box,
+                           float* score, int32_t* label, int32_t* pixel, int32_t* count, void* workspace, size_t workspace_bytes,
+                           shasta_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Public tracker step, device part: centre-distance matrix + greedy assignment for `scenes` independent scenes
  * replaces tools/nusc_shasta/pub_tracker.py:94-108 (`dist`, `invalid`, `dist + invalid * 1e18`) and

@@ -56,11 +56,29 @@ __device__ __forceinline__ float iou_axis_aligned(const float* a, const float* b
 // block = (64-column block cb, 64-row block rb), 4 waves: a wave takes rows r = wave, wave + 4, ...; lane j evaluates the pair
 // (row i, column 64 cb + j) and the wave's ballot IS the 64-bit mask word of that row (one thread per row with a 64-step
 // loop left most of the chip idle: 136 waves for 1000 boxes)
+// Segments (shasta_nms_rotated_batch_f32): blockIdx.z is the segment; its boxes are rows [offsets[z], offsets[z + 1]) of `boxes`, cut to
+// the first `n` (= the call's max_boxes), its mask rows are `words` words long and start at z * n * words.  offsets == nullptr: one
+// segment of n boxes (the single calls).
+struct NmsSegment {
+    int n;
+    size_t first;  // first box row
+};
+__device__ __forceinline__ NmsSegment nms_segment(const int32_t* __restrict__ offsets, int n) {
+    if (!offsets) return {n, 0};
+    const int a = offsets[blockIdx.z], b = offsets[blockIdx.z + 1];
+    return {max(0, min(b - a, n)), (size_t)a};
+}
+
 template <bool AXIS_ALIGNED>
-__global__ __launch_bounds__(256) void nms_mask_kernel(const float* __restrict__ boxes, int n, float thresh, int words,
-                                                       unsigned long long* __restrict__ mask) {
+__global__ __launch_bounds__(256) void nms_mask_kernel(const float* __restrict__ boxes, const int32_t* __restrict__ offsets, int n_max, float thresh,
+                                                       int words, unsigned long long* __restrict__ mask) {
     const int cb = blockIdx.x, rb = blockIdx.y;
     if (cb < rb) return;  // below the diagonal: never read
+    const NmsSegment sg = nms_segment(offsets, n_max);
+    const int n = sg.n;
+    if (cb * 64 >= n) return;  // (a segment shorter than the grid)
+    boxes += sg.first * 7;
+    mask += (size_t)blockIdx.z * n_max * words;
     __shared__ float col[64 * 7], row[64 * 7];
     const int ncol = min(64, n - cb * 64), nrow = min(64, n - rb * 64);
     for (int e = threadIdx.x; e < ncol * 7; e += 256) col[e] = boxes[(size_t)cb * 64 * 7 + e];
@@ -86,10 +104,14 @@ constexpr int NMS_MAX_WORDS_PER_LANE = 8;  // n <= 64 * 64 * 8 = 32768
 // the mask rows must not be: rows are fetched CH = 32 / SLOTS at a time (all loads of a chunk in flight together) and then
 // consumed from registers; a row-at-a-time version paid one global-load latency per box (0.57 us, 0.86 ms for 1000 boxes).
 template <int SLOTS>
-__global__ __launch_bounds__(64) void nms_reduce_kernel(const unsigned long long* __restrict__ mask, int n, int words,
-                                                        int* __restrict__ keep, int* __restrict__ num_keep) {
+__global__ __launch_bounds__(64) void nms_reduce_kernel(const unsigned long long* __restrict__ mask, const int32_t* __restrict__ offsets, int n_max,
+                                                        int words, int* __restrict__ keep, int* __restrict__ num_keep) {
     constexpr int CH = 32 / SLOTS;
     const int lane = threadIdx.x;
+    const int n = nms_segment(offsets, n_max).n, nwords = (n + 63) >> 6;  // words of a row that the mask kernel wrote
+    mask += (size_t)blockIdx.z * n_max * words;
+    keep += (size_t)blockIdx.z * n_max;
+    num_keep += blockIdx.z;
     unsigned long long removed[SLOTS];
 #pragma unroll
     for (int s = 0; s < SLOTS; ++s) removed[s] = 0ull;
@@ -103,7 +125,7 @@ __global__ __launch_bounds__(64) void nms_reduce_kernel(const unsigned long long
             for (int s = 0; s < SLOTS; ++s) {
                 const int w = lane + 64 * s;
                 // words left of the diagonal block were never written: treat as zero
-                buf[r][s] = (i < n && w < words && w >= (i >> 6)) ? mask[(size_t)i * words + w] : 0ull;
+                buf[r][s] = (i < n && w < nwords && w >= (i >> 6)) ? mask[(size_t)i * words + w] : 0ull;
             }
         }
 #pragma unroll
@@ -188,6 +210,24 @@ extern "C" size_t shasta_nms_workspace_bytes(int num_boxes) {
     return (size_t)std::max(num_boxes, 1) * words * sizeof(unsigned long long);
 }
 
+// the two launches over `segments` segments of at most n_max boxes (offsets == nullptr: one segment of exactly n_max)
+static int nms_launch(bool axis_aligned, const float* boxes, const int32_t* offsets, int segments, int n_max, float thresh,
+                      unsigned long long* mask, int32_t* keep, int32_t* num_keep, hipStream_t st) {
+    const int words = cdiv(n_max, 64);
+    if (axis_aligned)
+        hipLaunchKernelGGL(nms_mask_kernel<true>, dim3(words, words, segments), dim3(256), 0, st, boxes, offsets, n_max, thresh, words, mask);
+    else hipLaunchKernelGGL(nms_mask_kernel<false>, dim3(words, words, segments), dim3(256), 0, st, boxes, offsets, n_max, thresh, words, mask);
+    int rc = check_launch("nms_mask");
+    if (rc) return rc;
+    const int slots = cdiv(words, 64);
+    const dim3 grid(1, 1, segments);
+    if (slots <= 1) hipLaunchKernelGGL(nms_reduce_kernel<1>, grid, dim3(64), 0, st, mask, offsets, n_max, words, keep, num_keep);
+    else if (slots <= 2) hipLaunchKernelGGL(nms_reduce_kernel<2>, grid, dim3(64), 0, st, mask, offsets, n_max, words, keep, num_keep);
+    else if (slots <= 4) hipLaunchKernelGGL(nms_reduce_kernel<4>, grid, dim3(64), 0, st, mask, offsets, n_max, words, keep, num_keep);
+    else hipLaunchKernelGGL(nms_reduce_kernel<8>, grid, dim3(64), 0, st, mask, offsets, n_max, words, keep, num_keep);
+    return check_launch("nms_reduce");
+}
+
 static int nms_impl(bool axis_aligned, const float* boxes_sorted, int num_boxes, float thresh, void* workspace, size_t workspace_bytes,
                     int32_t* keep, int32_t* num_keep, shasta_stream_t stream) {
     SHASTA_REQUIRE(keep && num_keep && num_boxes >= 0, axis_aligned ? "nms_normal: bad argument" : "nms_rotated: bad argument");
@@ -206,18 +246,8 @@ static int nms_impl(bool axis_aligned, const float* boxes_sorted, int num_boxes,
         set_error_msg(axis_aligned ? "nms_normal: workspace too small" : "nms_rotated: workspace too small");
         return SHASTA_E_WORKSPACE;
     }
-    const int words = cdiv(num_boxes, 64);
     unsigned long long* mask = static_cast<unsigned long long*>(workspace);
-    if (axis_aligned) hipLaunchKernelGGL(nms_mask_kernel<true>, dim3(words, words), dim3(256), 0, st, boxes_sorted, num_boxes, thresh, words, mask);
-    else hipLaunchKernelGGL(nms_mask_kernel<false>, dim3(words, words), dim3(256), 0, st, boxes_sorted, num_boxes, thresh, words, mask);
-    int rc = check_launch("nms_mask");
-    if (rc) return rc;
-    const int slots = cdiv(words, 64);
-    if (slots <= 1) hipLaunchKernelGGL(nms_reduce_kernel<1>, dim3(1), dim3(64), 0, st, mask, num_boxes, words, keep, num_keep);
-    else if (slots <= 2) hipLaunchKernelGGL(nms_reduce_kernel<2>, dim3(1), dim3(64), 0, st, mask, num_boxes, words, keep, num_keep);
-    else if (slots <= 4) hipLaunchKernelGGL(nms_reduce_kernel<4>, dim3(1), dim3(64), 0, st, mask, num_boxes, words, keep, num_keep);
-    else hipLaunchKernelGGL(nms_reduce_kernel<8>, dim3(1), dim3(64), 0, st, mask, num_boxes, words, keep, num_keep);
-    return check_launch("nms_reduce");
+    return nms_launch(axis_aligned, boxes_sorted, nullptr, 1, num_boxes, thresh, mask, keep, num_keep, st);
 }
 
 extern "C" int shasta_nms_rotated_f32(const float* boxes_sorted, int num_boxes, float thresh, void* workspace, size_t workspace_bytes,
@@ -228,4 +258,34 @@ extern "C" int shasta_nms_rotated_f32(const float* boxes_sorted, int num_boxes, 
 extern "C" int shasta_nms_normal_f32(const float* boxes_sorted, int num_boxes, float thresh, void* workspace, size_t workspace_bytes,
                                      int32_t* keep, int32_t* num_keep, shasta_stream_t stream) {
     return nms_impl(true, boxes_sorted, num_boxes, thresh, workspace, workspace_bytes, keep, num_keep, stream);
+}
+
+// S segments of one sorted box array in one call: the kernels above with the segment as grid.z
+extern "C" size_t shasta_nms_batch_workspace_bytes(int segments, int max_boxes) {
+    if (segments < 1 || max_boxes < 1) return sizeof(unsigned long long);
+    return (size_t)segments * max_boxes * cdiv(max_boxes, 64) * sizeof(unsigned long long);
+}
+
+extern "C" int shasta_nms_rotated_batch_f32(const float* boxes_sorted, const int32_t* offsets, int segments, int max_boxes, float thresh,
+                                            void* workspace, size_t workspace_bytes, int32_t* keep, int32_t* num_keep, shasta_stream_t stream) {
+    SHASTA_REQUIRE(segments >= 0 && max_boxes >= 0, "nms_rotated_batch: bad argument");
+    SHASTA_REQUIRE(max_boxes <= 64 * 64 * NMS_MAX_WORDS_PER_LANE, "nms_rotated_batch: at most 32768 boxes per segment");
+    SHASTA_REQUIRE(segments <= 65535, "nms_rotated_batch: at most 65535 segments per call");
+    if (segments == 0) return SHASTA_OK;
+    SHASTA_REQUIRE(num_keep, "nms_rotated_batch: null pointer");
+    hipStream_t st = as_stream(stream);
+    if (max_boxes == 0) {
+        hipError_t e = hipMemsetAsync(num_keep, 0, (size_t)segments * sizeof(int32_t), st);
+        if (e != hipSuccess) {
+            set_error("nms_rotated_batch: memset", e);
+            return SHASTA_E_LAUNCH;
+        }
+        return SHASTA_OK;
+    }
+    SHASTA_REQUIRE(boxes_sorted && offsets && workspace && keep, "nms_rotated_batch: null pointer");
+    if (workspace_bytes < shasta_nms_batch_workspace_bytes(segments, max_boxes)) {
+        set_error_msg("nms_rotated_batch: workspace too small");
+        return SHASTA_E_WORKSPACE;
+    }
+    return nms_launch(false, boxes_sorted, offsets, segments, max_boxes, thresh, static_cast<unsigned long long*>(workspace), keep, num_keep, st);
 }

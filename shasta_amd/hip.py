@@ -45,6 +45,11 @@ class Weights(C.Structure):
                 ("aff", Linear * 6), ("aug_shape_aux", C.c_void_p), ("aug_shape_aux_bytes", C.c_size_t)]
 
 
+class HeadDecodeCfg(C.Structure):  # include/shasta_hip.h shasta_head_decode_cfg
+    _fields_ = [(n, C.c_int) for n in ("reg", "height", "dim", "rot", "vel", "hm", "num_class")] + \
+               [(n, C.c_float) for n in ("out_size_factor", "voxel_x", "voxel_y", "pc_x", "pc_y", "score_threshold")] + [("range", C.c_float * 6)]
+
+
 # every symbol include/shasta_hip.h declares: name -> (restype, argtypes)
 _P, _I, _F, _Z = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _WP = C.POINTER(Weights)
@@ -162,6 +167,13 @@ SYMBOLS = {
     "shasta_nms_rotated_f32": (_I, [_P, _I, _F, _P, _Z, _P, _P, _P]),
     "shasta_nms_normal_f32": (_I, [_P, _I, _F, _P, _Z, _P, _P, _P]),
     "shasta_boxes_bev_f32": (_I, [_P, _I, _P, _I, _I, _P, _P]),
+    "shasta_nms_batch_workspace_bytes": (_Z, [_I, _I]),
+    "shasta_nms_rotated_batch_f32": (_I, [_P, _P, _I, _I, _F, _P, _Z, _P, _P, _P]),
+    "shasta_head_supported": (_I, [_I, _I, _I, C.POINTER(C.c_int), _I, _I]),
+    "shasta_head_final_packed_bytes": (_Z, [_I]),
+    "shasta_head_final_f32": (_I, [_P, _I, _I, C.POINTER(C.c_int), _I, _I, _P, _Z, _P, _P]),
+    "shasta_head_decode_workspace_bytes": (_Z, [_I, _I, _I]),
+    "shasta_head_decode_f32": (_I, [_P, _I, _I, _I, _I, C.POINTER(HeadDecodeCfg), _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "shasta_center_greedy_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "shasta_track_merged_f64": (_I, [_P] * 9 + [_I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "shasta_track_merged_lsap_f64": (_I, [_P] * 9 + [_I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),

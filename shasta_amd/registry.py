@@ -62,4 +62,5 @@ def build_from_cfg(cfg, registry, default_args=None):
 
 
 READERS, BACKBONES, NECKS, TRACK, SECOND_STAGE, BEV = (Registry(n) for n in ("reader", "backbone", "neck", "track", "second_stage", "bev"))
+HEADS, DETECTORS = Registry("head"), Registry("detector")  # det3d/models/registry.py: CenterHead (shasta_amd/head.py), VoxelNet (detector.py)
 PIPELINES = Registry("pipeline")  # det3d/datasets/registry.py: the dataset pipeline steps (shasta_amd/sweeps.py)
