@@ -997,6 +997,108 @@ int shasta_sweeps_assemble_f32(const float* raw, long total_rows, int raw_ndim, 
                                int num_clouds, int keep, double radius, const shasta_sweep_augment* h_augment, float* out, long capacity,
                                int32_t* prefix, void* workspace, size_t workspace_bytes, shasta_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * CenterPoint training targets (csrc/center_targets.hip): ground-truth boxes -> heatmaps, anno_box, ind, mask, cat.  Restates the box
+ * half of det3d/datasets/pipelines/preprocess.py:126-136 (det3d/core/sampler/preprocess.py:771-839, 940-962), `filter_gt_box_outside_range`
+ * (sampler/preprocess.py:108-122) and `AssignLabel` (datasets/pipelines/preprocess.py:273-458), the nuScenes branch, for a batch of B samples
+ * and all T tasks in one call.  Boxes are (n, 9) fp32 rows [x, y, z, w, l, h, vx, vy, rot]; every step is fp32 arithmetic with separate
+ * roundings unless said otherwise.
+ *  augmentation (shasta_box_augment, per sample, in this order):
+ *    SHASTA_AUG_NEG_Y: y, vy -> -y, -vy; rot -> fl(-rot + fl32(pi)).   SHASTA_AUG_NEG_X: x, vx -> -x, -vx; rot -> fl(-rot + fl32(2 pi)).
+ *    rotation: (x, y) and (vx, vy) -> (fl(fl(a c) + fl(b s)), fl(fl(a (-s)) + fl(b c))), the order of shasta_sweeps_assemble_f32;
+ *              rot -> fl(rot + angle).   scale: columns 0 .. 7 -> fl32((double)v * scale) (the velocities too, as the reference does).
+ *    SHASTA_AUG_TRANSLATE: x, y, z -> fl32((double)v + translate[j]).
+ *  range filter: a box is kept iff one of its four BEV corners (fl(fl(+-w/2 cos) + fl(+-l/2 sin)) + x, fl(fl(+-w/2 (-sin)) + fl(+-l/2 cos)) + y,
+ *    sinf / cosf of rot) is strictly inside the rectangle [x0, y0, x1, y1]: for each directed edge the reference's cross product (fp32
+ *    products, float64 difference) must be < 0, so a corner exactly on an edge is OUTSIDE.  The upper corner is fl(fl(x1 - x0) + x0), as
+ *    minmax_to_corner_2d builds it.
+ *  assignment, per sample and task t (classes first .. first + num_class[t] - 1 of the 1-based input classes; first = 1 + the class counts
+ *    of the earlier tasks): the kept boxes of the task in class order, input order inside a class (stable partition); slot k = position in
+ *    that order; slots k >= max_objs are dropped.  rot -> limit_period(rot, 0.5, 2 pi) = fl(rot - fl(floor(fl(fl(rot / P) + 0.5)) P)),
+ *    P = fl32(2 pi).  w' = fl(fl(w / voxel_x) / osf), l' likewise with voxel_y; only w' > 0 && l' > 0 continues.  radius =
+ *    max(min_radius, (int)gaussian_radius((l', w'), overlap)), gaussian_radius in fp32 with the constants fl32(1 - o), fl32(1 + o),
+ *    fl32(-2 o), fl32(o - 1), fl32(16 o) (numpy >= 2 promotion).  ct = fl(fl(fl(x - pc_x) / voxel_x) / osf) (y likewise), ct_int its
+ *    truncation; a centre outside the map leaves slot k empty (mask 0).  Otherwise ind = ct_int.y map_w + ct_int.x, mask = 1,
+ *    cat = class - first, anno_box = [ct.x - ct_int.x, ct.y - ct_int.y, z, logf(w), logf(l), logf(h), vx, vy, sinf(rot), cosf(rot)], and
+ *    hm[cat] becomes the element-wise maximum with fl32(exp(-(dx^2 + dy^2) / (2 sigma sigma))), sigma = (2 r + 1) / 6, in float64, over the
+ *    (2 r + 1)^2 window clipped to the map: an integer atomicMax on the bit patterns of these non-negative floats - the same bits on
+ *    every run.  gt_boxes_and_cls (optional): row (boxes of earlier tasks + k) = columns [0, 1, 2, 3, 4, 5, 8, 6, 7] of the box (rot
+ *    limited) and the 1-based class over all tasks; rows >= max_objs are not written (the caller refuses such a sample).
+ *  Layouts: hm = the tasks back to back, task t a (B, num_class[t], map_h, map_w) fp32 block; anno_box (T, B, max_objs, 10) fp32;
+ *    ind, cat (T, B, max_objs) int64; mask (T, B, max_objs) uint8; gt_boxes_and_cls (B, max_objs, 10) fp32; boxes_out (n, 9) fp32 the
+ *    augmented boxes (rot NOT limited); keep_out (n,) uint8 the range filter's result (1 everywhere without one).  All outputs are
+ *    zeroed by the call.  h_offsets: HOST array of B + 1 row offsets into boxes / classes.
+ *  Served: 1 <= B <= 64, 1 <= T <= 16, 1 <= num_class[t] <= 4, 1 <= max_objs <= 1024, <= 4096 boxes per sample, maps up to 512 x 512;
+ *    anything beyond is SHASTA_E_UNSUPPORTED before any launch (workspace query: 0).
+ *  Chain: memsets -> copy of the tables -> one workgroup per sample (augment, filter, wave ballots + running class counts for the stable
+ *    rank, slots, anno_box / ind / mask / cat, one record per slot) -> one wave per slot draws its gaussian.  No host read.
+ * ------------------------------------------------------------------------------------------ */
+#define SHASTA_CENTER_MAX_BATCH 64
+#define SHASTA_CENTER_MAX_TASKS 16
+#define SHASTA_CENTER_MAX_TASK_CLASSES 4
+#define SHASTA_CENTER_MAX_OBJS 1024
+#define SHASTA_CENTER_MAX_BOXES 4096
+#define SHASTA_CENTER_MAX_MAP 512
+typedef struct shasta_box_augment {
+    int32_t flags; /* SHASTA_AUG_* */
+    float c, s;    /* cos and sin of the rotation angle, rounded to fp32 by the caller */
+    float angle;   /* the angle rounded to fp32: added to rot */
+    double scale;
+    double translate[3];
+} shasta_box_augment; /* 48 bytes */
+typedef struct shasta_center_target_cfg {
+    int32_t num_tasks;
+    int32_t num_class[SHASTA_CENTER_MAX_TASKS];
+    int32_t max_objs, min_radius;
+    int32_t map_w, map_h; /* feature_map_size[0], [1]: hm is (C, map_h, map_w) */
+    float pc_x, pc_y, voxel_x, voxel_y, out_size_factor;
+    double gaussian_overlap;
+} shasta_center_target_cfg;
+size_t shasta_center_targets_workspace_bytes(int B, int num_tasks, int max_objs);
+int shasta_center_targets_f32(const float* boxes, const int32_t* classes, const int32_t* h_offsets, int B,
+                              const shasta_center_target_cfg* cfg, const shasta_box_augment* h_augment, const float* h_bv_range,
+                              float* boxes_out, uint8_t* keep_out, float* hm, float* anno_box, int64_t* ind, uint8_t* mask, int64_t* cat,
+                              float* gt_boxes_and_cls, void* workspace, size_t workspace_bytes, shasta_stream_t stream);
+/* the two first stages alone: out (n, 9) = the augmented boxes (in place allowed); keep (n,) uint8.  n >= 0. */
+int shasta_center_box_augment_f32(const float* boxes, long n, const shasta_box_augment* h_augment, float* out, shasta_stream_t stream);
+int shasta_center_range_filter_f32(const float* boxes, long n, const float* h_bv_range, uint8_t* keep, shasta_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * CenterPoint head losses with their gradient (csrc/center_loss.hip), all T tasks of a batch in one chain, no host read.  Per task:
+ *   p = clamp(sigmoid(hm), 1e-4, 1 - 1e-4);  neg = sum log(1 - p) p^2 (1 - target)^4;  pos = sum_{b,k} mask log(q) (1 - q)^2 with
+ *   q = p[b, cat, ind];  num_pos = sum mask;  hm_loss = -(pos + neg) / num_pos, or -neg when num_pos == 0;
+ *   box_loss[c] = sum_{b,k} |pred mask - target mask| / (num_pos + 1e-4), pred gathered at ind from the channels (reg 2, height 1, dim 3,
+ *   vel 2, rot 2) = box[0 .. 4];  loc_loss = sum_c box_loss[c] code_weights[c];  loss = hm_loss + weight loc_loss.
+ * out (T, 14) fp32 on the device: [loss, hm_loss, loc_loss, box_loss[0 .. 9], num_pos].  g_hm (B, C, H, W) and g_box (B, 10, H, W), both
+ * contiguous, receive d loss / d hm and d loss / d (box channels in the order above): the dense pass reads every logit and target once
+ * and writes the focal term's gradient (zero where the clamp is active; the bounds themselves pass it, as torch.clamp does), then one
+ * workgroup per (sample, task) adds the <= max_objs positive terms: slots that share a pixel (and class) are summed in slot order by the
+ * first of them and stored once - no atomics, the same bits on every run.  Sums: float64 partials per workgroup, combined by one
+ * workgroup per task in a fixed tree.  Entries with mask != 0 whose ind / cat lie outside the map / the classes count in num_pos and
+ * contribute nothing else.
+ *  hm / box[i]: fp32, (B, channels, H, W) with the sample stride given in elements (a channel slice of a larger tensor is served),
+ *  channels and pixels contiguous.  target_hm (B, C, H, W), anno_box (B, max_objs, 10), ind / cat int64, mask uint8: contiguous.
+ * Served: 1 <= T <= 16, 1 <= B <= 64, 1 <= C <= 4, 1 <= max_objs <= 1024, H, W <= 512; beyond: SHASTA_E_UNSUPPORTED before any launch.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct shasta_center_loss_task {
+    const float* hm;
+    const float* target_hm;
+    const float* box[5];
+    const float* anno_box;
+    const int64_t* ind;
+    const int64_t* cat;
+    const uint8_t* mask;
+    float* g_hm;
+    float* g_box;
+    int64_t hm_stride;
+    int64_t box_stride[5];
+    int32_t num_class;
+    int32_t reserved;
+} shasta_center_loss_task; /* 160 bytes */
+size_t shasta_center_loss_workspace_bytes(int num_tasks, int B);
+int shasta_center_loss_f32(const shasta_center_loss_task* h_tasks, int num_tasks, int B, int H, int W, int max_objs, float weight,
+                           const float* h_code_weights, float* out, void* workspace, size_t workspace_bytes, shasta_stream_t stream);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus

@@ -12,6 +12,7 @@ from .head import CenterHead  # noqa: F401
 from .neck import RPN  # noqa: F401
 from .registry import BACKBONES, BEV, DETECTORS, HEADS, NECKS, PIPELINES, READERS, SECOND_STAGE, TRACK, Registry, build_from_cfg  # noqa: F401
 from .sweeps import LoadPointCloudFromFile, Preprocess, SweepClouds, assemble_clouds  # noqa: F401
+from .targets import AssignLabel, LoadPointCloudAnnotations, assign_targets  # noqa: F401
 from .shasta import Shasta, load_state_dict_permissive  # noqa: F401
 from .train_track import example_to_device, track_batch_processor  # noqa: F401
 from .voxel_encoder import VoxelFeatureExtractorV3  # noqa: F401

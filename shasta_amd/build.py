@@ -14,7 +14,8 @@ from concurrent.futures import ThreadPoolExecutor
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libshasta_hip.so")
 SOURCES = ["abi.hip", "bev_gather.hip", "gemm_f32.hip", "gemm_pieces.hip", "anchor.hip", "anchor_mfma.hip", "anchor_split.hip", "pair.hip", "pair_f16.hip", "pair_f16w.hip", "embed_rows.hip", "aff.hip", "aff_pieces.hip", "aff_f16.hip", "forward.hip",
-           "voxelize.hip", "dynvox.hip", "sweeps.hip", "shared_conv.hip", "shared_conv_f16.hip", "shared_conv_train.hip", "neck.hip", "sparse_conv.hip", "bn_rows.hip", "bn_maps.hip", "bn_sync.hip", "iou3d.hip", "decode.hip", "backward_aux.hip", "adam.hip", "bev_gather_bwd.hip", "pair_bwd.hip", "track.hip", "lsap.hip", "gt_labels.hip", "nms.hip", "head.hip"]
+           "voxelize.hip", "dynvox.hip", "sweeps.hip", "shared_conv.hip", "shared_conv_f16.hip", "shared_conv_train.hip", "neck.hip", "sparse_conv.hip", "bn_rows.hip", "bn_maps.hip", "bn_sync.hip", "iou3d.hip", "decode.hip", "backward_aux.hip", "adam.hip", "bev_gather_bwd.hip", "pair_bwd.hip", "track.hip", "lsap.hip", "gt_labels.hip", "nms.hip", "head.hip",
+           "center_targets.hip", "center_loss.hip"]
 # -ffp-contract=off: every fused multiply-add in the kernels is an explicit fmaf(); products that the
 # reference rounds separately stay separately rounded (parity with the PyTorch fp32 forward).
 # -fvisibility=hidden: the .so exports exactly the extern "C" functions include/shasta_hip.h declares (its visibility pragma)

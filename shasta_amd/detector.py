@@ -4,7 +4,9 @@ The reference keeps the socket (`DETECTORS`, `build_detector`, det3d/models/buil
 CenterPoint's `VoxelNet` on this package's modules.  Children are created in the order reader, backbone, neck, bbox_head, so a CenterPoint
 checkpoint's `reader.* / backbone.* / neck.* / bbox_head.*` keys load through `load_state_dict_permissive`.  `extract_feat` is `BEVMap`'s
 (both reader branches).  `forward(example, return_loss=False)` returns `bbox_head.predict(example, preds, test_cfg)`: one dict per sample
-`{box3d_lidar, scores, label_preds, metadata}`; `return_loss=True` raises NotImplementedError - there is no head loss here."""
+`{box3d_lidar, scores, label_preds, metadata}`; `return_loss=True` returns `bbox_head.loss(example, preds, test_cfg)`: one dict per task
+`{loss, hm_loss, loc_loss, loc_loss_elem, num_positive}`.  The loss needs the targets of `targets.AssignLabel` / `targets.assign_targets`
+in the example (`hm, anno_box, ind, mask, cat`); an example without them is refused with NotImplementedError before any stage runs."""
 from . import builder
 from .bevmap import BEVMap
 from .registry import DETECTORS
@@ -18,8 +20,11 @@ class VoxelNet(BEVMap):
         self.init_weights(pretrained=pretrained)
 
     def forward(self, example, return_loss=False, **kwargs):
-        if return_loss:
-            raise NotImplementedError("VoxelNet: the head's losses and target assignment are not part of this package")
+        if return_loss and any(k not in example for k in ("hm", "anno_box", "ind", "mask", "cat")):
+            raise NotImplementedError("VoxelNet: return_loss=True needs the targets hm, anno_box, ind, mask, cat in the example "
+                                      "(targets.AssignLabel / targets.assign_targets make them)")
         x, _ = self.extract_feat(example)
         preds = self.bbox_head(x)
+        if return_loss:
+            return self.bbox_head.loss(example, preds, self.test_cfg)
         return self.bbox_head.predict(example, preds, self.test_cfg)

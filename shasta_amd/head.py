@@ -5,8 +5,7 @@ source; this module restates CenterPoint's `CenterHead` / `SepHead` / `predict` 
 uses them.  Parameter names are the `bbox_head.*` keys of a CenterPoint checkpoint: `shared_conv.{0,1}.*`, `tasks.<t>.<head>.{0,1,3}.*`
 with the heads `reg, height, dim, rot, vel` (the order of `common_heads`) and `hm` last.  Initialisation: `hm`'s last bias is `init_bias`,
 every other convolution gets kaiming-normal weights and a zero bias; NO random-number parity with CenterPoint's construction is claimed
-(a checkpoint overwrites every tensor).  The loss arguments (`weight`, `code_weights`, `dataset`) are stored and unused: there is no
-head loss and no target assignment here.
+(a checkpoint overwrites every tensor).  The loss arguments (`weight`, `code_weights`, `dataset`) feed `loss`.
 
 `forward(x)` -> one dict per task, `{head name: (B, channels, H, W) fp32}`.  Two paths, `RPN`'s arrangement (neck.py):
   * the kernel path - `eval()` mode, fp32 device tensors, autograd off, `in_channels % 8 == 0`, `share_conv_channel % 32 == 0`, head width
@@ -24,7 +23,14 @@ device), a stable descending `torch.sort` of the scores (ties: the lower pixel f
 one copy of the counts to the host, and the cut to `nms_post_max_size`.  Tasks are concatenated in order, `label_preds` = label + the
 class count of the earlier tasks.  `max_per_img` is read and NOT applied: tasks x nms_post_max_size (6 x 83 = 498) stays below the
 nuScenes value of 500, as in CenterPoint.  `use_rotate_nms=False`, `use_multi_class_nms=True` and `dcn_head=True` raise
-NotImplementedError.  Circle NMS, the double-flip merge, the losses and graph capture are outside this module."""
+NotImplementedError.  Circle NMS, the double-flip merge and graph capture are outside this module.
+
+`loss(example, preds_dicts, test_cfg=None)` -> one dict per task `{loss, hm_loss, loc_loss, loc_loss_elem (10,), num_positive}`, device
+tensors: FastFocalLoss on `hm` and the masked L1 RegLoss on (reg, height, dim, vel, rot) against the targets of `targets.assign_targets`
+/ `AssignLabel` in `example` (`hm, anno_box, ind, mask, cat`), `loss = hm_loss + weight * loc_loss` (head_loss.py).  Both forms `forward`
+returns are accepted; fp32 device tensors take ONE `shasta_center_loss_f32` call for all tasks, which also leaves the gradient with respect
+to the raw outputs (head_loss.CenterLoss), everything else the torch composite.  In `train()` mode the convolutions run `forward_layers`
+under autograd: there is no convolution backward on the kernels.  nuScenes only."""
 import ctypes
 import math
 from collections import OrderedDict
@@ -83,7 +89,7 @@ class CenterHead(nn.Module):
         self.in_channels = int(in_channels[0] if isinstance(in_channels, (list, tuple)) else in_channels)
         self.num_classes = [int(t["num_class"]) for t in tasks]
         self.class_names = [list(t["class_names"]) for t in tasks]
-        self.dataset, self.weight, self.code_weights = dataset, weight, list(code_weights)  # loss arguments: stored, unused
+        self.dataset, self.weight, self.code_weights = dataset, weight, list(code_weights)  # loss arguments
         self.common_heads = OrderedDict((k, tuple(v)) for k, v in (common_heads if len(common_heads) else NUSC_COMMON_HEADS).items())
         self.share_conv_channel, self.num_hm_conv = int(share_conv_channel), int(num_hm_conv)
 
@@ -262,6 +268,21 @@ class CenterHead(nn.Module):
                 at += k
             rets.append(d)
         return rets
+
+    # ---- losses -------------------------------------------------------------------------------------------------
+    def loss(self, example, preds_dicts, test_cfg=None, **kwargs):
+        from . import head_loss
+        if str(self.dataset).lower() not in ("nuscenes", "nuscenesdataset"):
+            raise NotImplementedError("CenterHead.loss: only nuScenes is served (dataset=%r)" % (self.dataset,))
+        if len(preds_dicts) != len(self.tasks):
+            raise ValueError("CenterHead.loss: %d prediction dicts for %d tasks" % (len(preds_dicts), len(self.tasks)))
+        missing = [k for k in ("hm", "anno_box", "ind", "mask", "cat") if k not in example]
+        if missing:
+            raise NotImplementedError("CenterHead.loss: a loss without targets is not served - the example lacks %s (targets.AssignLabel / "
+                                      "targets.assign_targets make them)" % missing)
+        if len(self.code_weights) != 10:
+            raise ValueError("CenterHead.loss: code_weights must hold ten values, one per anno_box channel (got %d)" % len(self.code_weights))
+        return head_loss.center_loss(preds_dicts, example, self.weight, self.code_weights)
 
     # ---- detections ---------------------------------------------------------------------------------------------
     @torch.no_grad()

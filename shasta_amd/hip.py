@@ -50,6 +50,22 @@ class HeadDecodeCfg(C.Structure):  # include/shasta_hip.h shasta_head_decode_cfg
                [(n, C.c_float) for n in ("out_size_factor", "voxel_x", "voxel_y", "pc_x", "pc_y", "score_threshold")] + [("range", C.c_float * 6)]
 
 
+class BoxAugment(C.Structure):  # include/shasta_hip.h shasta_box_augment
+    _fields_ = [("flags", C.c_int32), ("c", C.c_float), ("s", C.c_float), ("angle", C.c_float), ("scale", C.c_double), ("translate", C.c_double * 3)]
+
+
+class CenterTargetCfg(C.Structure):  # include/shasta_hip.h shasta_center_target_cfg
+    _fields_ = [("num_tasks", C.c_int32), ("num_class", C.c_int32 * 16), ("max_objs", C.c_int32), ("min_radius", C.c_int32),
+                ("map_w", C.c_int32), ("map_h", C.c_int32)] + \
+               [(n, C.c_float) for n in ("pc_x", "pc_y", "voxel_x", "voxel_y", "out_size_factor")] + [("gaussian_overlap", C.c_double)]
+
+
+class CenterLossTask(C.Structure):  # include/shasta_hip.h shasta_center_loss_task
+    _fields_ = [("hm", C.c_void_p), ("target_hm", C.c_void_p), ("box", C.c_void_p * 5), ("anno_box", C.c_void_p), ("ind", C.c_void_p),
+                ("cat", C.c_void_p), ("mask", C.c_void_p), ("g_hm", C.c_void_p), ("g_box", C.c_void_p), ("hm_stride", C.c_int64),
+                ("box_stride", C.c_int64 * 5), ("num_class", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every symbol include/shasta_hip.h declares: name -> (restype, argtypes)
 _P, _I, _F, _Z = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _WP = C.POINTER(Weights)
@@ -65,6 +81,12 @@ SYMBOLS = {
     "shasta_dynvox_mean_f32": (_I, [_P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _Z, _P]),
     "shasta_sweeps_workspace_bytes": (_Z, [_I, C.c_long]),
     "shasta_sweeps_assemble_f32": (_I, [_P, C.c_long, _I, _P, _I, _I, _I, C.c_double, _P, _P, C.c_long, _P, _P, _Z, _P]),
+    "shasta_center_targets_workspace_bytes": (_Z, [_I, _I, _I]),
+    "shasta_center_targets_f32": (_I, [_P, _P, _P, _I, C.POINTER(CenterTargetCfg), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "shasta_center_box_augment_f32": (_I, [_P, C.c_long, C.POINTER(BoxAugment), _P, _P]),
+    "shasta_center_range_filter_f32": (_I, [_P, C.c_long, _P, _P, _P]),
+    "shasta_center_loss_workspace_bytes": (_Z, [_I, _I]),
+    "shasta_center_loss_f32": (_I, [_P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _Z, _P]),
     "shasta_voxel_mean_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "shasta_bev_gather_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _P, _I, _I, _P]),
     "shasta_shared_conv_packed_bytes": (_Z, [_I]),

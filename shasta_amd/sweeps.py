@@ -16,7 +16,8 @@ rotation by a non-zero angle, which the reference leaves to its BLAS (DESIGN.md 
 Deviations, all deliberate:
   * the reference's hard-coded `.replace('tsadja', 'ubuntu')` on every path is not copied: pass `path_map`, a callable str -> str.
   * `WaymoDataset`, `res["virtual"]`, a `db_sampler` and `min_points_in_gt > 0` raise NotImplementedError.
-  * `Preprocess` handles the points only: ShaSTA never reads the pipeline's `gt_boxes`.
+  * `Preprocess` works on the ground-truth boxes only when res["lidar"]["annotations"] is present (targets.py applies the drawn entry
+    to them); without annotations it handles the points alone, as the tracker's pipeline needs.
 There is no CPU path: CPU use raises ShastaHipError."""
 import ctypes as C
 import os
@@ -227,10 +228,15 @@ def draw_augment(rot_noise, scale_noise, translate_std):
 
 @PIPELINES.register_module
 class Preprocess(object):
-    """preprocess.py:28-158, points only.  In train mode (without `no_augmentation`) the parameters are drawn by `draw_augment` and
+    """preprocess.py:28-158.  In train mode (without `no_augmentation`) the parameters are drawn by `draw_augment` and
     applied by the assembly kernels' write pass to res["lidar"]["combined"]; with `shuffle_points` the permutation is drawn with
     `np.random.shuffle` on an index array - the same permutation as shuffling the rows - and applied as a row gather.  Result in
-    res["lidar"]["points"], as in the reference; the drawn parameters are kept in res["lidar"]["augment"]."""
+    res["lidar"]["points"], as in the reference; the drawn parameters are kept in res["lidar"]["augment"].
+    With res["lidar"]["annotations"] (`LoadPointCloudAnnotations`) in train mode the boxes follow the reference too: `DontCare / ignore /
+    UNKNOWN` are dropped, the `class_names` mask and the 1-based `gt_classes` are built on the host, the SAME drawn entry is applied to the
+    boxes on the device (`targets.augment_boxes`), and `gt_dict` (`gt_boxes` a device tensor, `gt_names`, `gt_classes`) replaces
+    res["lidar"]["annotations"]; with `no_augmentation` the classes are selected and numbered only.  The draws and the points do not
+    depend on the presence of annotations."""
 
     def __init__(self, cfg=None, **kwargs):
         self.shuffle_points = _get(cfg, "shuffle_points")
@@ -256,18 +262,42 @@ class Preprocess(object):
         points = res["lidar"]["combined"]
         if not (torch.is_tensor(points) and points.is_cuda):
             raise hip.ShastaHipError("Preprocess needs the device tensor LoadPointCloudFromFile leaves; there is no CPU path")
+        gt_dict = None
+        if self.mode == "train" and "annotations" in res["lidar"]:
+            anno = res["lidar"]["annotations"]
+            gt_dict = {"gt_boxes": anno["boxes"], "gt_names": np.array(anno["names"]).reshape(-1)}
+            if not self.no_augmentation:
+                self._select(gt_dict, np.array([n not in ("DontCare", "ignore", "UNKNOWN") for n in gt_dict["gt_names"]], dtype=np.bool_))
+            self._select(gt_dict, np.array([n in self.class_names for n in gt_dict["gt_names"]], dtype=np.bool_))
+            gt_dict["gt_classes"] = np.array([self.class_names.index(n) + 1 for n in gt_dict["gt_names"]], dtype=np.int32)
+            boxes = gt_dict["gt_boxes"]
+            if not torch.is_tensor(boxes):
+                boxes = torch.from_numpy(np.ascontiguousarray(boxes, dtype=np.float32))
+            gt_dict["gt_boxes"] = boxes.to(points.device, torch.float32).reshape(-1, 9)
         if self.mode == "train" and not self.no_augmentation:
             entry = draw_augment(self.global_rotation_noise, self.global_scaling_noise, self.global_translate_std)
             n, w = int(points.shape[0]), int(points.shape[1])
             out, _ = assemble_rows(points, [(n, 0, None, False, 0.0)], 1, keep=w, augment=[entry])  # no row is dropped
             points = out[:n, :w].contiguous()
             res["lidar"]["augment"] = entry
+            if gt_dict is not None:
+                from .targets import augment_boxes
+                gt_dict["gt_boxes"] = augment_boxes(gt_dict["gt_boxes"], entry)
         if self.shuffle_points:
             index = np.arange(int(points.shape[0]))
             np.random.shuffle(index)
             points = points[torch.from_numpy(index).to(points.device)]
         res["lidar"]["points"] = points
+        if gt_dict is not None:
+            res["lidar"]["annotations"] = gt_dict
         return res, info
+
+    @staticmethod
+    def _select(gt_dict, keep):
+        """_dict_select on the host arrays (the boxes are still the loader's numpy array or a tensor of any device)."""
+        boxes = gt_dict["gt_boxes"]
+        gt_dict["gt_boxes"] = boxes[torch.from_numpy(keep).to(boxes.device)] if torch.is_tensor(boxes) else boxes[keep]
+        gt_dict["gt_names"] = gt_dict["gt_names"][keep]
 
 
 class SweepClouds:
