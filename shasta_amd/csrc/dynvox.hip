@@ -113,31 +113,8 @@ __global__ void dv_prefix_kernel(const uint32_t* __restrict__ bits, const uint32
         num_voxels[n] = (int)sums[nblk];
         return;
     }
-    const int lin = c * cells_per_cloud, w = lin >> 5;
-    num_voxels[c] = (int)(sums[w / SC_SCAN] + pre[w] + __popc(bits[w] & ((1u << (lin & 31)) - 1u)));
-}
-
-// one thread per bitmap word: the coordinates of its set bits at their ranks (rows >= capacity are not written)
-__global__ void dv_emit_kernel(const uint32_t* __restrict__ bits, const uint32_t* __restrict__ pre, const uint32_t* __restrict__ sums,
-                               size_t words, int D, int H, int W, int capacity, int* __restrict__ coors) {
-    const size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= words) return;
-    uint32_t word = bits[w];
-    if (!word) return;
-    int rank = (int)(sums[w / SC_SCAN] + pre[w]);
-    while (word && rank < capacity) {
-        const int bit = __ffs(word) - 1;
-        word &= word - 1;
-        int lin = (int)(w * 32) + bit;
-        const int x = lin % W;
-        lin /= W;
-        const int y = lin % H;
-        lin /= H;
-        const int z = lin % D, b = lin / D;
-        int* c = coors + 4 * (size_t)rank;
-        c[0] = b, c[1] = z, c[2] = y, c[3] = x;
-        ++rank;
-    }
+    const int lin = c * cells_per_cloud;
+    num_voxels[c] = sp_rank_below(bits[lin >> 5], pre, sums, lin);
 }
 
 // keys[i]: linear cell -> row of the voxel; slot[i] = the point's place in its voxel's list (arrival order: any permutation)
@@ -153,21 +130,9 @@ __global__ __launch_bounds__(256) void dv_count_kernel(int* __restrict__ keys, l
     if (r >= 0 && r < P) slot[gi] = atomicAdd(&cnt[r], 1);
 }
 
-// per scan block of 1024 counts: exclusive prefix inside the block, the block's total
-__global__ __launch_bounds__(256) void dv_scan_counts_kernel(const int* __restrict__ cnt, int* __restrict__ cpre, uint32_t* __restrict__ csum) {
-    __shared__ uint32_t s_wave[4];
-    const size_t w0 = (size_t)blockIdx.x * SC_SCAN + 4 * threadIdx.x;
-    const u32x4 v = *reinterpret_cast<const u32x4*>(cnt + w0);
-    uint32_t total;
-    const uint32_t ex = sp_block_scan(v[0] + v[1] + v[2] + v[3], s_wave, &total);
-    u32x4 o;
-    o[0] = ex, o[1] = ex + v[0], o[2] = ex + v[0] + v[1], o[3] = ex + v[0] + v[1] + v[2];
-    *reinterpret_cast<u32x4*>(cpre + w0) = o;
-    if (threadIdx.x == 0) csum[blockIdx.x] = total;
-}
-
+// first entry of voxel v's list in seg: the points of the voxels before it (cnt scanned into cpre, csum by scan.hpp's two kernels)
 __device__ __forceinline__ int dv_start(const int* __restrict__ cpre, const uint32_t* __restrict__ csum, int v) {
-    return (int)csum[v / SC_SCAN] + cpre[v];
+    return (int)scan_prefix(reinterpret_cast<const uint32_t*>(cpre), csum, (size_t)v);
 }
 
 __global__ __launch_bounds__(256) void dv_fill_kernel(const int* __restrict__ row, const int* __restrict__ slot, long P,
@@ -371,13 +336,14 @@ extern "C" int shasta_dynvox_mean_f32(const float* points, const int* h_offsets,
     if ((rc = sp_scan(ix, nullptr, st))) return rc;
     hipLaunchKernelGGL(dv_prefix_kernel, dim3(1), dim3(64), 0, st, ix.bits, ix.pre, ix.sums, num_clouds, D * H * W, ix.nblk, num_voxels);
     if (capacity > 0)
-        hipLaunchKernelGGL(dv_emit_kernel, dim3((unsigned)((ix.words + 255) / 256)), dim3(256), 0, st, ix.bits, ix.pre, ix.sums, ix.words, D, H,
-                           W, capacity, coors);
-    if ((rc = check_launch("dv_emit"))) return rc;
+        hipLaunchKernelGGL(sp_index_emit_kernel, dim3((unsigned)((ix.words + 255) / 256)), dim3(256), 0, st, ix.bits, ix.pre, ix.sums, ix.words,
+                           D, H, W, capacity, coors, (int*)nullptr);
+    if ((rc = check_launch("sp_index_emit"))) return rc;
     if (capacity == 0) return SHASTA_OK;
     hipLaunchKernelGGL(dv_count_kernel, dim3(pblocks), dim3(256), 0, st, L.row, P, ix.bits, ix.pre, ix.sums, L.slot, L.cnt);
-    hipLaunchKernelGGL(dv_scan_counts_kernel, dim3(L.cblk), dim3(256), 0, st, L.cnt, L.cpre, L.csum);
-    hipLaunchKernelGGL(sp_scan_sums_kernel, dim3(1), dim3(256), 0, st, L.csum, L.cblk, (int*)nullptr);
+    hipLaunchKernelGGL(scan_blocks_kernel<false>, dim3(L.cblk), dim3(256), 0, st, reinterpret_cast<const uint32_t*>(L.cnt),
+                       reinterpret_cast<uint32_t*>(L.cpre), L.csum);
+    hipLaunchKernelGGL(scan_sums_kernel<true>, dim3(1), dim3(256), 0, st, L.csum, L.cblk, (int32_t*)nullptr);
     hipLaunchKernelGGL(dv_fill_kernel, dim3(pblocks), dim3(256), 0, st, L.row, L.slot, P, L.cpre, L.csum, L.seg);
     if ((rc = check_launch("dv_fill"))) return rc;
     const long rows = P < capacity ? P : capacity;  // V <= P

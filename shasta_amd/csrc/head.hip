@@ -19,9 +19,10 @@
 //
 // 2. shasta_head_decode_f32 - one task's raw maps to a compacted candidate list per image, in ascending pixel order, counts on the
 //    device: count (one pixel per thread, wave ballot -> a block's count), scan (one workgroup per image over its block counts), write
-//    (the flags recomputed by the same function, place = block offset + lower waves + lower lanes).  No atomics.
+//    (the flags recomputed by the same function, place = block offset + lower waves + lower lanes).  No atomics.  The ballot step and
+//    the scan kernel are scan.hpp's.
 #include "common.hpp"
-#include "sp_index.hpp"
+#include "scan.hpp"
 
 namespace shasta {
 
@@ -141,26 +142,8 @@ __global__ __launch_bounds__(256) void head_decode_count_kernel(const float* __r
     const int t = threadIdx.x, b = blockIdx.y, p = blockIdx.x * 256 + t;
     bool keep = false;
     if (p < npix) keep = head_decode_pixel(raw + (size_t)b * C * npix, npix, W, p, cfg).keep;
-    const int wave_kept = __popcll(__ballot(keep));
-    if ((t & 63) == 0) s_wave[t >> 6] = wave_kept;
-    __syncthreads();
-    if (t == 0) cnt[(size_t)b * gridDim.x + blockIdx.x] = (uint32_t)(s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3]);
-}
-
-// one workgroup per image: cnt[b][:] -> its exclusive scan in place, count[b] = the image's candidates
-__global__ __launch_bounds__(256) void head_decode_scan_kernel(uint32_t* __restrict__ cnt, int nblk, int32_t* __restrict__ count) {
-    __shared__ uint32_t s_wave[4];
-    uint32_t* c = cnt + (size_t)blockIdx.x * nblk;
-    uint32_t carry = 0;
-    for (int base = 0; base < nblk; base += 256) {
-        const int j = base + threadIdx.x;
-        const uint32_t v = j < nblk ? c[j] : 0u;
-        uint32_t total;
-        const uint32_t ex = sp_block_scan(v, s_wave, &total);
-        if (j < nblk) c[j] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) count[blockIdx.x] = (int32_t)carry;
+    const int kept = block_place(keep, s_wave).count;
+    if (t == 0) cnt[(size_t)b * gridDim.x + blockIdx.x] = (uint32_t)kept;
 }
 
 __global__ __launch_bounds__(256) void head_decode_write_kernel(const float* __restrict__ raw, int C, int npix, int W, shasta_head_decode_cfg cfg,
@@ -171,13 +154,9 @@ __global__ __launch_bounds__(256) void head_decode_write_kernel(const float* __r
     DecodedPixel d;
     d.keep = false;
     if (p < npix) d = head_decode_pixel(raw + (size_t)b * C * npix, npix, W, p, cfg);
-    const unsigned long long ballot = __ballot(d.keep);
-    const int lane = t & 63, wv = t >> 6;
-    if (lane == 0) s_wave[wv] = __popcll(ballot);
-    __syncthreads();
-    if (!d.keep) return;
-    long place = (long)off[(size_t)b * gridDim.x + blockIdx.x] + __popcll(ballot & ((1ull << lane) - 1ull));
-    for (int j = 0; j < wv; ++j) place += s_wave[j];
+    const BlockPlace bp = block_place(d.keep, s_wave);
+    if (!d.keep) return;  // (after the barrier inside block_place)
+    const long place = (long)off[(size_t)b * gridDim.x + blockIdx.x] + bp.place;
     if (place >= cap) return;  // counted, not written
     const size_t at = (size_t)b * cap + place;
 #pragma unroll
@@ -267,7 +246,7 @@ extern "C" int shasta_head_decode_f32(const float* raw, int B, int C, int H, int
     hipLaunchKernelGGL(head_decode_count_kernel, dim3(nblk, B), dim3(256), 0, st, raw, C, npix, W, *cfg, cnt);
     int rc = check_launch("head_decode_count");
     if (rc) return rc;
-    hipLaunchKernelGGL(head_decode_scan_kernel, dim3(B), dim3(256), 0, st, cnt, nblk, count);
+    hipLaunchKernelGGL(scan_sums_kernel<false>, dim3(B), dim3(256), 0, st, cnt, nblk, count);  // one workgroup per image: count[b] = its candidates
     rc = check_launch("head_decode_scan");
     if (rc) return rc;
     if (cap == 0) return SHASTA_OK;

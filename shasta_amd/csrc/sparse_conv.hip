@@ -34,7 +34,7 @@
 // Packed layer: [tap][Cin rounded up to 8][Cout] weights (from the spconv 2.x layout (Cout, kD, kH, kW, Cin); channels >= Cin are
 // zeros), then alpha[Cout], beta'[Cout]: alpha = gamma / sqrt(var + eps), beta' = beta + (bias - mean) * alpha.
 #include "common.hpp"
-#include "sp_index.hpp"  // SpIndex, sp_rank, the two scan kernels (shared with dynvox.hip)
+#include "sp_index.hpp"  // SpIndex, sp_rank, sp_scan, the emit kernel (shared with dynvox.hip)
 
 namespace shasta {
 
@@ -97,30 +97,6 @@ __global__ void sp_perm_rows_kernel(const int* __restrict__ coords, int n, int B
     if ((unsigned)b >= (unsigned)B || (unsigned)z >= (unsigned)D || (unsigned)y >= (unsigned)H || (unsigned)x >= (unsigned)W) return;
     const int r = sp_rank(bits, pre, sums, ((b * D + z) * H + y) * W + x);
     if (r >= 0 && r < n) perm[r] = i;  // (unique coordinates: every rank below the count is written once)
-}
-
-// one thread per bitmap word: the coordinates of its set bits at their ranks, perm = identity
-__global__ void sp_emit_kernel(const uint32_t* __restrict__ bits, const uint32_t* __restrict__ pre, const uint32_t* __restrict__ sums,
-                               size_t words, int D, int H, int W, int capacity, int* __restrict__ coords, int* __restrict__ perm) {
-    const size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= words) return;
-    uint32_t word = bits[w];
-    if (!word) return;
-    int rank = (int)(sums[w / SC_SCAN] + pre[w]);
-    while (word && rank < capacity) {
-        const int bit = __ffs(word) - 1;
-        word &= word - 1;
-        int lin = (int)(w * 32) + bit;
-        const int x = lin % W;
-        lin /= W;
-        const int y = lin % H;
-        lin /= H;
-        const int z = lin % D, b = lin / D;
-        int* c = coords + 4 * (size_t)rank;
-        c[0] = b, c[1] = z, c[2] = y, c[3] = x;
-        perm[rank] = rank;
-        ++rank;
-    }
 }
 
 // one thread per (output row, tap): the input row at o * s - p + t, or -1
@@ -394,8 +370,8 @@ extern "C" int shasta_spconv_out_coords(const int* coords, int n_in, int B, int 
     const int rc = sp_scan(ix, n_out, st);
     if (rc != SHASTA_OK) return rc;
     if (out_capacity > 0)
-        hipLaunchKernelGGL(sp_emit_kernel, dim3((unsigned)((ix.words + 255) / 256)), dim3(256), 0, st, ix.bits, ix.pre, ix.sums, ix.words, Do,
-                           Ho, Wo, out_capacity, out_coords, ix.perm);
+        hipLaunchKernelGGL(sp_index_emit_kernel, dim3((unsigned)((ix.words + 255) / 256)), dim3(256), 0, st, ix.bits, ix.pre, ix.sums, ix.words,
+                           Do, Ho, Wo, out_capacity, out_coords, ix.perm);
     return check_launch("spconv_out_coords");
 }
 

@@ -34,7 +34,7 @@
 //               The row stride in LDS is raw_ndim / keep + 1 words; for the nuScenes widths (5 and 5) the lanes of a half wave hit
 //               32 different banks.
 #include "common.hpp"
-#include "sp_index.hpp"
+#include "scan.hpp"
 #include <limits.h>
 #include <math.h>
 
@@ -44,7 +44,7 @@ constexpr int SW_ROWS = SHASTA_SWEEPS_BLOCK_ROWS;  // rows per block = threads p
 constexpr int SW_MAX_CLOUDS = SHASTA_SWEEPS_MAX_CLOUDS;
 constexpr int SW_MAX_SEGMENTS = SHASTA_SWEEPS_MAX_SEGMENTS;
 constexpr int SW_MIN_NDIM = 3, SW_MAX_NDIM = 8;
-static_assert(SW_ROWS == 256, "the kernels below use sp_block_scan: 256 threads");
+static_assert(SW_ROWS == SCAN_THREADS, "the kernels below use scan.hpp: 256 threads");
 static_assert(sizeof(shasta_sweep_segment) == 120 && sizeof(shasta_sweep_augment) == 48, "table layouts");
 
 struct SwPlan {
@@ -91,8 +91,8 @@ __global__ __launch_bounds__(256) void sw_plan_kernel(const shasta_sweep_segment
         k[q] = (r[q] + SW_ROWS - 1) / SW_ROWS;
     }
     uint32_t rows_total, blk_total;
-    uint32_t er = sp_block_scan(r[0] + r[1] + r[2] + r[3], s_wave, &rows_total);
-    uint32_t ek = sp_block_scan(k[0] + k[1] + k[2] + k[3], s_wave, &blk_total);
+    uint32_t er = block_scan(r[0] + r[1] + r[2] + r[3], s_wave, &rows_total);
+    uint32_t ek = block_scan(k[0] + k[1] + k[2] + k[3], s_wave, &blk_total);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int s = 4 * t + q;
@@ -135,10 +135,8 @@ __global__ __launch_bounds__(256) void sw_count_kernel(const uint32_t* __restric
         const uint32_t* p = raw + ((size_t)plan->row0[s] + local) * raw_ndim;
         keep = sw_keep(p[0], p[1], seg[s].flags & SHASTA_SWEEP_DROP_CLOSE, radius);
     }
-    const int wave_kept = __popcll(__ballot(keep));
-    if ((t & 63) == 0) s_wave[t >> 6] = wave_kept;
-    __syncthreads();
-    if (t == 0) cnt[b] = (uint32_t)(s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3]);
+    const int kept = block_place(keep, s_wave).count;
+    if (t == 0) cnt[b] = (uint32_t)kept;
 }
 
 // one workgroup: off[b] = kept rows before block b; prefix[c] = kept rows before cloud c, prefix[n] = all kept rows
@@ -148,20 +146,12 @@ __global__ __launch_bounds__(256) void sw_scan_kernel(const uint32_t* __restrict
     __shared__ int s_first[SW_MAX_CLOUDS + 1];
     if (threadIdx.x <= n) s_first[threadIdx.x] = plan->cloud_blk[threadIdx.x];
     __syncthreads();
-    uint32_t carry = 0;
-    for (int base = 0; base < nblk; base += 256) {
-        const int j = base + threadIdx.x;
-        const uint32_t v = j < nblk ? cnt[j] : 0u;
-        uint32_t total;
-        const uint32_t ex = sp_block_scan(v, s_wave, &total);
-        if (j < nblk) {
-            off[j] = carry + ex;
-            for (int c = 0; c <= n; ++c)
-                if (s_first[c] == j) prefix[c] = (int32_t)(carry + ex);
-        }
-        carry += total;
-    }
-    if (threadIdx.x <= n && s_first[threadIdx.x] >= nblk) prefix[threadIdx.x] = (int32_t)carry;
+    const uint32_t total = scan_with_carry(cnt, nblk, s_wave, [&](int j, uint32_t ex) {
+        off[j] = ex;
+        for (int c = 0; c <= n; ++c)
+            if (s_first[c] == j) prefix[c] = (int32_t)ex;
+    });
+    if (threadIdx.x <= n && s_first[threadIdx.x] >= nblk) prefix[threadIdx.x] = (int32_t)total;
 }
 
 __global__ __launch_bounds__(256) void sw_write_kernel(const uint32_t* __restrict__ raw, int raw_ndim, const shasta_sweep_segment* __restrict__ seg,
@@ -185,13 +175,8 @@ __global__ __launch_bounds__(256) void sw_write_kernel(const uint32_t* __restric
         for (int j = 0; j < SW_MAX_NDIM; ++j) v[j] = j < raw_ndim ? s_in[t * raw_ndim + j] : 0u;
         keep = sw_keep(v[0], v[1], flags & SHASTA_SWEEP_DROP_CLOSE, radius);
     }
-    const unsigned long long ballot = __ballot(keep);
-    const int lane = t & 63, wv = t >> 6;
-    if (lane == 0) s_wave[wv] = __popcll(ballot);
-    __syncthreads();
-    int place = __popcll(ballot & ((1ull << lane) - 1ull));
-    for (int j = 0; j < wv; ++j) place += s_wave[j];
-    const int kept = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    const BlockPlace bp = block_place(keep, s_wave);
+    const int place = bp.place, kept = bp.count;
     const int ow = keep_cols + 1;
     if (keep) {
         if (flags & SHASTA_SWEEP_TRANSFORM) {

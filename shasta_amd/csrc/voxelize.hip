@@ -21,6 +21,7 @@
 // 2^ceil(log2(2 P)) (key, first point) entries per cloud (8 MB for 3e5 points), cleared by one memset per call - random accesses over
 // 5.3 GB of dense maps (16 clouds) were most of the chain's time (TLB and DRAM page misses on every point).
 #include "common.hpp"
+#include "scan.hpp"
 #include <math.h>
 #include <limits.h>
 
@@ -131,6 +132,7 @@ __global__ __launch_bounds__(256) void vox_owner_kernel(const int* __restrict__ 
 }
 
 // single block: exclusive scan of block_sums[0..n) in place; block_sums[n] = total
+// (not scan.hpp's 256-wide carry loop: about 19 000 block sums per batch at the shipped shape, a timed path; 1024 threads, a chunk each)
 __global__ __launch_bounds__(1024) void vox_scan_kernel(int* __restrict__ block_sums, int n) {
     __shared__ int part[1024];
     const int t = threadIdx.x;
@@ -164,15 +166,9 @@ __global__ __launch_bounds__(256) void vox_assign_kernel(const int* __restrict__
     __shared__ int wave_cnt[4];
     int c, i;
     vox_locate(B, blockIdx.x, threadIdx.x, c, i);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const size_t gi = (size_t)B.off[c] + max(i, 0);
     const bool flag = i >= 0 && owner[gi] == i;
-    const unsigned long long m = __ballot(flag);
-    if (lane == 0) wave_cnt[wid] = __popcll(m);
-    __syncthreads();
-    int off = block_sums[blockIdx.x] - block_sums[B.boff[c]];
-    for (int w = 0; w < wid; ++w) off += wave_cnt[w];
-    const int vid = off + __popcll(m & ((1ull << lane) - 1ull));
+    const int vid = block_sums[blockIdx.x] - block_sums[B.boff[c]] + block_place(flag, wave_cnt).place;
     if (flag) {
         vid_of_point[gi] = vid;
         if (vid < max_voxels) {

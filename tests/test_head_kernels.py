@@ -187,6 +187,31 @@ def test_decode_batch_with_an_empty_sample_in_the_middle_and_class_ties():
     assert all(torch.equal(got[k], again[k]) for k in got), "two runs differ"
 
 
+# a 257 x 256 map of 0.6 m pixels: every row inside in y, the border columns outside in x
+DECODE_CFG_TALL = dict(HH.DECODE_CFG, post_center_limit_range=[-37.0, -3.0, -5.0, 113.0, 152.0, 3.0])
+
+
+def test_decode_second_trip_of_the_block_count_scan():
+    """257 x 256 pixels = exactly 257 blocks per image: the scan of an image's block counts makes a second trip of its carry loop, which
+    holds one block.  Image 0 keeps pixels in the first block, in the last block of the first trip and in the block of the second;
+    image 1 has another count, so a carry that survived from image 0 would show."""
+    H, W, nc = 257, 256, 2
+    assert H * W == 257 * 256
+    cases = [HH.decode_input(n, H, W, nc, seed, DECODE_CFG_TALL) for n, seed in ((3000, 1257), (300, 2391))]
+    raw = torch.stack([c[0] for c in cases])
+    oracles = [c[1] for c in cases]
+    assert all(o["margin_score"] > 1e-4 and o["margin_range"] > 1e-3 for o in oracles)
+    blocks = (oracles[0]["pixel"] // 256).tolist()
+    assert 0 in blocks and 255 in blocks and 256 in blocks and blocks[-1] == 256 and int(oracles[0]["pixel"][-1]) >= 65536
+    assert [len(o["pixel"]) for o in oracles] == [3000, 300]  # (the counts differ: the carry starts at 0 for every image)
+    _, bars = HH.transcendental_bars(raw, nc)
+    got = _decode(raw, nc, DECODE_CFG_TALL)
+    again = _decode(raw, nc, DECODE_CFG_TALL)
+    for b in range(2):
+        _check_decoded(got, b, oracles[b], bars, H, W, DECODE_CFG_TALL, "image %d" % b)
+    assert all(torch.equal(got[k], again[k]) for k in got), "two runs differ"
+
+
 # ---- batched NMS ------------------------------------------------------------------------------------------------------
 
 def _segments(sizes, seed):

@@ -319,6 +319,27 @@ def test_seams_through_the_c_abi_bit_for_bit():
 
 
 @pytest.mark.gpu
+def test_second_trip_of_the_block_count_scan_bit_for_bit():
+    """Cloud 0 is 257 blocks: the scan of the block counts makes a second trip of its carry loop.  Its sweep holds blocks 255 and 256 - it
+    straddles the two trips - with dropped rows at both ends of block 255 and in the one row of block 256; cloud 1 is block 257, so
+    prefix[1] is read at a block of the second trip and prefix[2] is the carry after it."""
+    R, rng = 256, np.random.default_rng(11)
+    close = [0.5, -0.25]
+    key = _rows(rng, 255 * R, "mix")     # blocks 0 .. 254; the key frame is never filtered
+    sweep = _rows(rng, R + 1, "far")     # blocks 255 and 256
+    sweep[[0, R - 1, R], :2] = close
+    T = np.array([[0.8, -0.6, 0.0, 1.5], [0.6, 0.8, 0.0, -0.25], [0.0, 0.0, 1.0, 0.1], [0, 0, 0, 1]], np.float64)
+    raw, segs = _flatten([(key, [(sweep, T, 0.05)]), (_rows(rng, 70, "mix"), [])])
+    want, want_prefix = H.assemble(raw, segs, 2)
+    assert [s[0] for s in segs] == [255 * R, R + 1, 70]
+    assert want_prefix.tolist() == [0, 255 * R + R - 2, 255 * R + R - 2 + 70]
+    got, prefix = _run_abi(raw, segs, 2)
+    _check(got, prefix, want, want_prefix)
+    again, prefix2 = _run_abi(raw, segs, 2)
+    assert np.array_equal(got, again) and np.array_equal(prefix, prefix2)
+
+
+@pytest.mark.gpu
 def test_empty_inputs_through_the_c_abi():
     raw = np.zeros((0, 5), np.float32)
     got, prefix = _run_abi(raw, [H.segment(0, 0), H.segment(0, 1, np.eye(4), True, 0.1)], 2)
