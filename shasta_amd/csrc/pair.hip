@@ -125,6 +125,7 @@ struct RowPrepArgs {
     const float* tab[2];  // [0] prev_tab, [1] det_tab   (B, T, 8)
     float* emb[2];        // [0] UP, [1] UC             (B, T, ET)
     float* hand[2];       // (B, T, 16)
+    float* sel;           // (B, T, PAIR_SEL_ROW): S[t] of the previous side (select role, F = 256)
     float* denom;         // (B, D)
     int B, T, N, nf, F, nrow_blocks, nhand_blocks, dblocks, dper;  // dper: detections per thread of the column-norm role (1 or 4)
 };
@@ -306,6 +307,64 @@ __global__ __launch_bounds__(256) void row_prep_kernel(RowPrepArgs a) {
     }
 }
 
+// The select role (F = 256, "f16x2"): pair_f16_kernel<PAIR_SELECT> forms relu(u + v) as max(v, -u) + u from pre-cut words
+// (pieces.hpp, cut_select_word) and needs, per track row, what the "+ u" contributes behind the linear second layers:
+//     S[t][j] = bias2[j] + sum_k W2[j][k] UP[t][k],     j in the order [res_coeff.2 16 | fuse_shape.2 16 | fuse_det.2 8].
+// It is formed from the SAME operands the MFMAs see - u as the value of the word of -UP[t][k] (cut under the row's own range
+// exponent: a word's pieces do not depend on the power of two it was cut under, except where the low piece is an fp16 denormal or the
+// value is flushed, 2^-39 and 2^-28 of the range), W2 as the sum of its two fp16 pieces (wsum, pair_f16_pack_kernel) -, so that an
+// inactive unit (u + v < 0: the MFMAs deliver W (-u)) cancels in the operands and leaves only accumulation rounding.  Every product
+// is exact in float64; the sum runs over k in ascending order, one chain per output, and is rounded to fp32 once, with the bias.
+// A kernel of its own like col_norm_kernel (14 KB of float64 weights + 16 KB of rows in LDS); it runs behind row_prep, whose row role
+// completes UP and the row maxima.  32 table rows per round: thread (r = tid & 31, g = tid >> 5) cuts columns 16 g .. 16 g + 15 of
+// row r, then computes 4 outputs x 64 k (g < 4: res_coeff), 8 x 32 (g = 4, 5: fuse_shape; g = 6: fuse_det); g = 7 only cuts.
+constexpr int SEL_ROUNDS = 4;
+__global__ __launch_bounds__(256) void row_select_kernel(RowPrepArgs a) {
+    constexpr int F = 256;
+    __shared__ __attribute__((aligned(16))) double wd[PAIR_SEL_SUM];  // [k][j]: rc [64][16] | fs [32][16] | fd [32][8]
+    __shared__ float xs[32][129];
+    const int tid = threadIdx.x, r = tid & 31, g = tid >> 5;
+    const PackedLayout P(a.N, a.nf, F);
+    const float* wsum = a.packed + P.p16 + P16_SUM_DW;
+    const int* ew = reinterpret_cast<const int*>(a.packed + P.p16 + P16_FRAG_DW);  // fs, rc, fd
+    for (int e = tid; e < PAIR_SEL_SUM; e += 256) wd[e] = (double)wsum[e];
+    // this thread's outputs (uniform per wave but for the idle g = 7)
+    const int nout = g < 4 ? 4 : g < 7 ? 8 : 0, kn = g < 4 ? 64 : 32, x0 = g < 4 ? 32 : g < 6 ? 0 : 96;
+    const int wstride = g < 6 ? 16 : 8, jo = g < 4 ? 4 * g : g < 6 ? 16 + 8 * (g - 4) : 32;  // first output, in S's order
+    const double* wb = wd + (g < 4 ? 4 * g : g < 6 ? 1024 + 8 * (g - 4) : 1536);
+    const int layer = g < 4 ? L_RC2 : g < 6 ? L_FS2 : L_FD2, j0 = g < 4 ? 4 * g : g < 6 ? 8 * (g - 4) : 0;
+    const float* bias = a.packed + P.a4 + a4_offset(F, layer) + a4_nob(F, layer) * a4_kg(F, layer) * 16 + j0;
+    const int ewm = ew[g < 4 ? 1 : g < 6 ? 0 : 2];
+    const int rows = a.B * a.T;
+    for (int it = 0; it < SEL_ROUNDS; ++it) {
+        const int row = ((int)blockIdx.x * SEL_ROUNDS + it) * 32 + r, rowc = min(row, rows - 1);
+        __syncthreads();  // the weights are staged / the previous round's rows have been read
+        const int er = range_exponent_bits(__float_as_uint(a.hand[0][(size_t)rowc * 16 + 13]));
+        {
+            const f32x4* up = reinterpret_cast<const f32x4*>(a.emb[0] + (size_t)rowc * 128 + 16 * g);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const f32x4 v = up[q];
+#pragma unroll
+                for (int z = 0; z < 4; ++z) xs[r][16 * g + 4 * q + z] = select_word_value(cut_select_word(__builtin_ldexpf(-v[z], er)));
+            }
+        }
+        __syncthreads();
+        double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int k = 0; k < kn; ++k) {
+            const double x = (double)xs[r][x0 + k];
+#pragma unroll
+            for (int o = 0; o < 8; ++o)
+                if (o < nout) acc[o] = __builtin_fma(x, wb[k * wstride + o], acc[o]);
+        }
+        // x stands for -UP 2^er and the weights carry 2^ewm: S = bias - acc 2^-(er + ewm)
+        if (row < rows)
+#pragma unroll
+            for (int o = 0; o < 8; ++o)
+                if (o < nout) a.sel[(size_t)row * PAIR_SEL_ROW + jo + o] = (float)((double)bias[o] - __builtin_ldexp(acc[o], -(er + ewm)));
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // pair_mfma4: lane = pair, layers 2-4 on v_mfma_f32_4x4x1_16B_f32 (16 independent 4x4 blocks per instruction:
 // block = 4 consecutive lanes = 4 pairs, 4 output features, K = 1; 8.4 cycles measured, the same MAC rate as 16x16x4).
@@ -482,6 +541,7 @@ int pair_residual(const shasta_weights* w, const float* packed, int B, const flo
     float* UC = reinterpret_cast<float*>(base + L.uc);
     float* hand_prev = reinterpret_cast<float*>(base + L.hand_prev);
     float* hand_det = reinterpret_cast<float*>(base + L.hand_det);
+    float* sel_prev = reinterpret_cast<float*>(base + L.sel_prev);
     float* denom = reinterpret_cast<float*>(base + L.denom);
 
     // row embeddings UP / UC: from 8192 table rows one fused kernel per launch forms the feature part on the bf16-piece matrix path,
@@ -504,6 +564,7 @@ int pair_residual(const shasta_weights* w, const float* packed, int B, const flo
     rp.emb[1] = UC;
     rp.hand[0] = hand_prev;
     rp.hand[1] = hand_det;
+    rp.sel = sel_prev;
     rp.denom = denom;
     rp.B = B;
     rp.T = T;
@@ -529,8 +590,12 @@ int pair_residual(const shasta_weights* w, const float* packed, int B, const flo
         // second layers of the three pair MLPs on the f16 matrix path (pair_f16.hip), everything else as below
         if (ev0) (void)hipEventRecord(ev0, st);
         // SHASTA_OPT_F16GRID_PAIR: the fixed-grid form (needs the per-MLP row maxima that only the fused row-embedding kernel writes)
-        const bool grid = (w->options & SHASTA_OPT_F16GRID_PAIR) != 0 && fused;
-        rc = launch_pair_f16(packed, packed + P.p16, UP, UC, hand_prev, hand_det, denom, residual, B, T, D, ld, nf, grid, st);
+        const PairF16Mode mode = (w->options & SHASTA_OPT_F16GRID_PAIR) != 0 && fused ? PAIR_GRID : PAIR_SELECT;
+        if (mode == PAIR_SELECT) {  // the tracks' S[t] (inside the events: the select form's own cost)
+            hipLaunchKernelGGL(row_select_kernel, dim3(cdiv(B * T, 32 * SEL_ROUNDS)), dim3(256), 0, st, rp);
+            if ((rc = check_launch("row_select"))) return rc;
+        }
+        rc = launch_pair_f16(packed, packed + P.p16, UP, UC, hand_prev, hand_det, sel_prev, denom, residual, B, T, D, ld, nf, mode, st);
         if (ev1) (void)hipEventRecord(ev1, st);
         return rc;
     }

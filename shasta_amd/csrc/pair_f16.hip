@@ -6,19 +6,33 @@
 // layers behind it.  Arithmetic: the two-piece fp16 form of pieces.hpp (three products), three v_mfma_f32_16x16x32_f16 instead of
 // sixteen f32 4x4x1 MFMA slots per 16 x 16 x 32 block; fp32 accumulation.
 //
-// Layouts.  A wave owns 64 detections x a range of tracks (as before).  Per track:
-//  (1) four sub-steps of 16 detections in the MFMA layout lane = (pair p = lane & 15, k block kb = lane >> 4): the lane forms
-//      h1[32 s + 8 kb + j], j < 8, for the four 32-wide k steps s (fuse_shape | res_coeff lower half | upper half | fuse_det) from
-//      8 UP values (LDS broadcast, read once per track) and 8 UC values (LDS) each - ReLU and range scaling are one packed
-//      v_pk_fma_f32 with clamp per two values (fma2_relu01) -, multiplies by 2^14 (packed), converts (v_cvt_pk_f16_f32), takes the
-//      residual (v_fma_mix_f32: x - h with h as an f16 operand, exact) and converts it: 2.5 issue slots of 5 - 8 cycles per value;
-//      12 MFMAs; the three result blocks (4 consecutive output features of pair p per lane) go to a wave-private LDS tile
+// Two forms of the pieces of h1 (PairF16Mode): PAIR_SELECT, the "f16x2" default, and PAIR_GRID ("f16grid", opt-in, further down).
+//
+// PAIR_SELECT does not cut per pair.  relu(u + v) = max(v, -u) + u with u = UP[t][k], v = UC[d][k]: max(v, -u) is one of two numbers
+// that exist per table ROW, so their fp16 pieces are cut once - UC[d] when the detection tile is loaded, -UP[t] once per track by
+// its wave - into one orderable 32-bit word per value (pieces.hpp: cut_select_word), and per pair and hidden unit ONE v_max_f32 picks
+// the word of the larger value.  The "+ u" passes through the linear second layers as S[t] = bias2 + W2 UP[t], 40 floats per track
+// row (pair.hip: row_select_kernel), the addend of the descale fma in phase (2).  Unlike a fixed grid every word keeps the relative
+// precision of its own value (tools/pair_quant_sim.py `select`: max / rms error 1.0 - 1.2 x the f32 kernel's).
+//
+// Layouts.  A wave owns 64 detections x a range of tracks.  Per track:
+//  (1) four sub-steps of 16 detections in the MFMA layout lane = (pair p = lane & 15, k block kb = lane >> 4).  A word is [hi | lo]
+//      of ONE real k, so an instruction's 32 k are 16 real k: the lane holds words 16 c + 4 kb + jj, jj < 4, of instruction c < 8
+//      (c = 0, 1 fuse_shape | 2 .. 5 res_coeff | 6, 7 fuse_det), and the weight fragments hold every weight twice ([Wh|Wh], [Wl|Wl]:
+//      all four piece products).  Per sub-step: 8 ds_read_b128 of UC words, 32 v_max_f32 in place, 16 MFMAs (12 in the per-pair cut
+//      this replaced); the three result blocks (4 consecutive output features of pair p per lane) go to a wave-private LDS tile
 //      [64 pairs][40 features].
-//  (2) lane = pair: the lane reads its 40 layer-2 pre-activations, descales (exact power of two) and adds the bias with one
-//      fma each, and runs layers 3-4, the hand-designed residual and the combine exactly as pair_mfma4_kernel does.
-// Range: the scale 2^e of a track is the one that puts (max |UP[t]| + max over the tile's detections of max |UC[d]|) - an upper
-// bound of every h1 of the sub-steps - into (2^13, 2^14]; the row maxima come from embed_rows / row_prep (slot 13 of the hand rows).  The
-// second-layer weights are cut once at pack time with one exponent per MLP (pair_f16_pack_kernel).
+//  (2) lane = pair: the lane reads its 40 layer-2 pre-activations, descales (exact power of two) and adds S[t] with one fma each,
+//      and runs layers 3-4, the hand-designed residual and the combine exactly as pair_mfma4_kernel does.
+// Range: ONE scale 2^e per (workgroup's tracks, detection tile) - two words are only comparable under the same scale -, the one
+// that puts (largest finite max |UP[t]| of the workgroup's tracks + largest max |UC[d]| of the tile) into (2^13, 2^14]; the row
+// maxima come from embed_rows / row_prep (slot 13 of the hand rows).  The second-layer weights are cut once at pack time with one
+// exponent per MLP (pair_f16_pack_kernel).
+// Counted in the ISA: 311 vector instructions per track and wave (184 of them v_max_f32; the per-pair cut had 552, 384 of them
+// conversions, mixes and packed fp32 ops), 64 + 69 MFMAs (48 + 69), 234 registers, two waves per SIMD.  Measured at 1024
+// frame-pairs, N = M = 500 (profiles/pair_select_ab.txt): pair stage by events, row_select_kernel included, 8.20 - 8.26 -> 7.58 - 7.79
+// ms with the tracks still dealt 1000 : 615, 7.47 - 7.82 ms dealt 1000 : 760 (launch_pair_f16).  Far less than the instruction count:
+// the vector pipe is no longer the limit; per track and wave the LDS now serves ~85 b128 reads and 12 b128 writes.
 #include "stages.hpp"
 #include "pair_lane.hpp"
 #include "pieces.hpp"
@@ -31,8 +45,12 @@ namespace shasta {
 // ---- pack: the three second layers as A operands of v_mfma_f32_16x16x32_f16 -----------------------------------------------
 // fragments (1 KB each = [64 lanes][8 fp16]): 0 fuse_shape.2 (16 x 32) | 1, 2 res_coeff.2 (16 x 64, two k steps) | 3 fuse_det.2
 // (8 x 32, rows 8..15 zero); lane (i = lane & 15, kb = lane >> 4) holds W[i][32 ks + 8 kb + j] * 2^e_mlp; high pieces then low pieces.
-// layout (dwords): [piece 2][fragment 4][lane 64][4], then 3 int exponents (fs, rc, fd), padded to 4.
-constexpr int P16_FRAG_DW = 2 * 4 * 64 * 4;
+// layout (dwords): [piece 2][fragment 4][lane 64][4], then 3 int exponents (fs, rc, fd), padded to 4 (P16_FRAG_DW, pair_layout.hpp).
+// Behind them, in the p16w section (free at F = 256), for PAIR_SELECT (P16_SEL_DW): [piece 2][instruction 8][lane 64][4].  An activation word is [hi | lo] of ONE real k, so
+// an instruction's 32 k are 16 real k, each twice: lane (i, kb) holds W[i][16 c + 4 kb + jj] 2^e_mlp, jj < 4, in BOTH halves of dword
+// jj - the fragments [Wh|Wh] and [Wl|Wl], all four piece products.  c = 0, 1 fuse_shape.2 | 2 .. 5 res_coeff.2 | 6, 7 fuse_det.2.
+// And (P16_SUM_DW) float wsum = high + low piece (exact in fp32) as [k][j] per MLP: what row_select_kernel multiplies a track's
+// words by.
 
 __global__ __launch_bounds__(256) void pair_f16_pack_kernel(PairF16PackArgs a) {
     __shared__ float red[3][4];
@@ -49,6 +67,31 @@ __global__ __launch_bounds__(256) void pair_f16_pack_kernel(PairF16PackArgs a) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = i < rows ? __builtin_ldexpf(W[mlp][i * kin + 32 * ks + 8 * kb + j], ex[mlp]) : 0.0f;
     store_weight_pieces(v, a.out, 4, frag, lane);
+    // select fragments: two instructions per wave
+    for (int c = 2 * frag; c < 2 * frag + 2; ++c) {
+        const int m = c < 2 ? 0 : c < 6 ? 1 : 2, c0 = c < 2 ? 0 : c < 6 ? 2 : 6;
+        const int mrows = m == 2 ? 8 : 16, mkin = m == 1 ? 64 : 32;
+        u32x4 hi, lo;
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+            const float x = i < mrows ? __builtin_ldexpf(W[m][i * mkin + 16 * (c - c0) + 4 * kb + jj], ex[m]) : 0.0f;
+            _Float16 h, l;
+            cut2_f16(x, h, l);
+            hi[jj] = pack_f16x2(h, h);
+            lo[jj] = pack_f16x2(l, l);
+        }
+        reinterpret_cast<u32x4*>(a.out + P16_SEL_DW)[(0 * 8 + c) * 64 + lane] = hi;
+        reinterpret_cast<u32x4*>(a.out + P16_SEL_DW)[(1 * 8 + c) * 64 + lane] = lo;
+    }
+    float* wsum = reinterpret_cast<float*>(a.out + P16_SUM_DW);
+    for (int e = tid; e < PAIR_SEL_SUM; e += 256) {
+        // [k][j]: rc [64][16] | fs [32][16] | fd [32][8]
+        const int m = e < 1024 ? 1 : e < 1536 ? 0 : 2, el = e < 1024 ? e : e < 1536 ? e - 1024 : e - 1536;
+        const int nj = m == 2 ? 8 : 16, mkin = m == 1 ? 64 : 32, k = el / nj, j = el - k * nj;
+        _Float16 h, l;
+        cut2_f16(__builtin_ldexpf(W[m][j * mkin + k], ex[m]), h, l);
+        wsum[e] = (float)h + (float)l;
+    }
 }
 
 int pair_f16_pack(const shasta_weights* w, float* out, hipStream_t st) {
@@ -63,8 +106,9 @@ constexpr int GR_ROW = 136;  // GRID: fp16 per row of the detection tile: 128 + 
 // dynamic LDS of pair_f16_kernel (float offsets): the kernel carves it, the launcher sizes it.  GRID: the detection tile holds fp16
 // pieces - [64][GR_ROW] high pieces, then the same of low pieces, 1 KB more than the fp32 tile - and every wave has a row of UP pieces
 // behind the transposition tiles
-template <int WPB, bool GRID>
+template <int WPB, PairF16Mode MODE>
 struct PairF16Lds {
+    static constexpr bool GRID = MODE == PAIR_GRID, SEL = MODE == PAIR_SELECT;
     static constexpr int US = PairDims(256).ET + 4;               // floats per row of the fp32 detection tile
     static constexpr int uc = 0;                                  // [64][US], GRID: [2][64][GR_ROW / 2] words
     static constexpr int ucl = uc + 64 * (GR_ROW / 2);            // GRID: the low pieces
@@ -72,10 +116,14 @@ struct PairF16Lds {
     static constexpr int a4 = uc + (GRID ? 2 * 64 * (GR_ROW / 2) : 64 * US);
     static constexpr int up = a4 + pad4(a4_total(256));           // [WPB][3 slots][UP_SLOT]
     static constexpr int tr = up + WPB * 3 * UP_SLOT;             // [WPB][64 pairs][PF_TS]
-    static constexpr int upp = tr + WPB * 64 * PF_TS;             // GRID: [WPB][2][64] words
-    static constexpr size_t bytes = (size_t)(upp + (GRID ? WPB * 128 : 0)) * sizeof(float);
+    static constexpr int upp = tr + WPB * 64 * PF_TS;             // GRID: [WPB][2][64] words; SEL: [WPB][128] words
+    static constexpr size_t bytes = (size_t)(upp + (GRID || SEL ? WPB * 128 : 0)) * sizeof(float);
 };
-static_assert(PairF16Lds<8, false>::bytes == 156912 && PairF16Lds<8, true>::bytes == 162032, "the sizes the launcher spelt out before");
+// PAIR_SELECT: the detection tile holds select words in the fp32 tile's layout and size, and every wave a row of its track's words
+static_assert(PairF16Lds<8, PAIR_GRID>::bytes == 162032 && PairF16Lds<8, PAIR_SELECT>::bytes == 161008, "the sizes the launcher spells out");
+// floats of a wave's UP slot: [ET row embeddings | 16 hand floats | PAIR_SEL_ROW floats S[t] (PAIR_SELECT)]
+constexpr int UPS_SEL = 128 + 16;
+static_assert(UPS_SEL + PAIR_SEL_ROW <= UP_SLOT);
 
 // GRID (SHASTA_OPT_F16GRID_PAIR, opt-in): the pieces of h1 are not cut per pair.  UP[t] and UC[d] are cut ONCE per row into two
 // fp16 pieces on a common fixed grid per MLP - high piece an integer, low piece a multiple of 2^-11, after scaling the largest
@@ -86,22 +134,22 @@ static_assert(PairF16Lds<8, false>::bytes == 156912 && PairF16Lds<8, true>::byte
 // (tools/pair_quant_sim.py: max / rms error of `residual` 2x / 5x the fp32 kernels', 1e-6 of its range), which is why this is
 // not the default arithmetic.
 
-template <int WPB, bool GRID>
+template <int WPB, PairF16Mode MODE>
 __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restrict__ packed, const uint32_t* __restrict__ p16,
                                                        const float* __restrict__ UP, const float* __restrict__ UC,
                                                        const float* __restrict__ hand_prev, const float* __restrict__ hand_det,
-                                                       const float* __restrict__ denom, float* __restrict__ residual, int T,
+                                                       const float* __restrict__ sel_prev, const float* __restrict__ denom, float* __restrict__ residual, int T,
                                                        int D, int ld, int nf, int TWG, int TA, int TB) {
     // TWG tracks per workgroup: TA to each of the waves 0 .. 3, TB to each of the waves 4 .. 7 (launch_pair_f16: the two waves of a
     // SIMD do not advance at the same rate)
     constexpr int F = 256;
+    constexpr bool GRID = MODE == PAIR_GRID, SEL = MODE == PAIR_SELECT;
     constexpr PairDims dm(F);
     constexpr int ET = dm.ET;
     static_assert(dm.H1 == 32 && dm.R1 == 64 && ET == 128 && dm.H2 == 16 && dm.R2 == 16, "pair_f16_kernel is laid out for F = 256");
-    using Lds = PairF16Lds<WPB, GRID>;
+    using Lds = PairF16Lds<WPB, MODE>;
     constexpr int US = Lds::US;
     extern __shared__ __attribute__((aligned(16))) float s_dynh[];
-    float* s_uc = s_dynh + Lds::uc;
     float* s_a4 = s_dynh + Lds::a4;
     float* s_up = s_dynh + Lds::up;
     float* s_tr = s_dynh + Lds::tr;
@@ -118,17 +166,6 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
     const int d0 = lbx * 64;
     const int d = d0 + lane, dcl = min(d, D - 1);
     {
-        if constexpr (!GRID) {
-            const f32x4* src = reinterpret_cast<const f32x4*>(UC);
-#pragma unroll 4
-            for (int e = tid; e < 64 * (ET / 4); e += 64 * WPB) {
-                const int r = e / (ET / 4), c = e - r * (ET / 4);
-                // float4 c of the row = k step c >> 3, k block (c >> 1) & 3, half c & 1: stored k-block-major, the blocks in the order
-                // 0, 2, 1, 3 (see load_uc: blocks 0 / 1 and 2 / 3 must sit 64 floats apart)
-                const int cp = (((c >> 1) & 1) << 4) | (((c >> 2) & 1) << 3) | ((c >> 3) << 1) | (c & 1);
-                *reinterpret_cast<f32x4*>(&s_uc[r * US + 4 * cp]) = src[((size_t)b * D + min(d0 + r, D - 1)) * (ET / 4) + c];
-            }
-        }
         a4_stage<F, 64 * WPB>(packed, s_a4, tid);
     }
     float hd[12];
@@ -203,12 +240,59 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
                 pu2{__builtin_bit_cast(uint32_t, ph2t{ll[0], ll[1]}), __builtin_bit_cast(uint32_t, ph2t{ll[2], ll[3]})};
         }
     }
-    // second-layer weight pieces: 4 fragments x {high, low}, registers for the whole kernel
-    u32x4 wh[4], wl[4];
+    // PAIR_SELECT: ONE scale for all tracks of this workgroup and the detections of this tile - the exponent that puts (largest finite
+    // |UP| of the workgroup's tracks + largest |UC| of the tile) into (2^13, 2^14] -, because a pair's two words must be comparable.
+    // A track whose own maximum is not finite takes no part in it (it gets NaN below, its neighbours keep their scale); a non-finite
+    // tile maximum makes the bound non-finite: NaN for the tile.
+    int e_sel = 0;
+    bool sel_finite = true;
+    uint32_t* s_ucw = reinterpret_cast<uint32_t*>(s_dynh + Lds::uc);  // the tile as select words, laid out like the fp32 tile
+    if constexpr (SEL) {
+        float mu = 0.0f;
+        const int tw0 = by * TWG, tw1 = min(T, tw0 + TWG);
+        for (int t = tw0 + tid; t < tw1; t += 64 * WPB) {
+            const float m = hand_prev[((size_t)b * T + t) * 16 + 13];
+            if (m < INFINITY) mu = fmaxf(mu, m);
+        }
 #pragma unroll
-    for (int f = 0; f < 4; ++f) {
-        wh[f] = reinterpret_cast<const u32x4*>(p16)[(0 * 4 + f) * 64 + lane];
-        wl[f] = reinterpret_cast<const u32x4*>(p16)[(1 * 4 + f) * 64 + lane];
+        for (int off = 32; off > 0; off >>= 1) mu = fmaxf(mu, __shfl_xor(mu, off, 64));
+        float* red = s_tr;  // scratch: the transposition tiles are not in use yet
+        if (lane == 0) red[wid] = mu;
+        __syncthreads();
+        mu = red[0];
+        for (int w = 1; w < WPB; ++w) mu = fmaxf(mu, red[w]);
+        const float bound = mu + mc;
+        sel_finite = bound < INFINITY;  // false for NaN and +inf
+        e_sel = range_exponent_bits(__float_as_uint(bound));
+        __syncthreads();  // red is read by everyone before the tiles are written
+        const f32x4* src = reinterpret_cast<const f32x4*>(UC);
+#pragma unroll 2
+        for (int e = tid; e < 64 * (ET / 4); e += 64 * WPB) {
+            const int r = e / (ET / 4), c = e - r * (ET / 4);
+            // float4 c of the row = the four real k of MFMA instruction c >> 2, k block c & 3: stored k-block-major, the blocks in the
+            // order 0, 2, 1, 3 and 64 words apart in pairs - the fp32 tile's bank layout (load_uc below), read with the same addresses
+            const int cp = ((c & 1) << 6) | (((c >> 1) & 1) << 5) | ((c >> 2) << 2);
+            const f32x4 v = src[((size_t)b * D + min(d0 + r, D - 1)) * (ET / 4) + c];
+            *reinterpret_cast<u32x4*>(&s_ucw[r * US + cp]) =
+                u32x4{cut_select_word(__builtin_ldexpf(v[0], e_sel)), cut_select_word(__builtin_ldexpf(v[1], e_sel)),
+                      cut_select_word(__builtin_ldexpf(v[2], e_sel)), cut_select_word(__builtin_ldexpf(v[3], e_sel))};
+        }
+    }
+    // second-layer weight pieces: 4 fragments x {high, low} (PAIR_SELECT: 8 instructions x {[Wh|Wh], [Wl|Wl]}), registers for the
+    // whole kernel
+    u32x4 wh[4], wl[4], sh[8], sl[8];
+    if constexpr (SEL) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            sh[c] = reinterpret_cast<const u32x4*>(p16 + P16_SEL_DW)[(0 * 8 + c) * 64 + lane];
+            sl[c] = reinterpret_cast<const u32x4*>(p16 + P16_SEL_DW)[(1 * 8 + c) * 64 + lane];
+        }
+    } else {
+#pragma unroll
+        for (int f = 0; f < 4; ++f) {
+            wh[f] = reinterpret_cast<const u32x4*>(p16)[(0 * 4 + f) * 64 + lane];
+            wl[f] = reinterpret_cast<const u32x4*>(p16)[(1 * 4 + f) * 64 + lane];
+        }
     }
     const int ew_fs = reinterpret_cast<const int*>(p16)[P16_FRAG_DW + 0], ew_rc = reinterpret_cast<const int*>(p16)[P16_FRAG_DW + 1],
               ew_fd = reinterpret_cast<const int*>(p16)[P16_FRAG_DW + 2];
@@ -222,11 +306,12 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
     const int t_end = min(min(T, (by + 1) * TWG), t_beg + (wid < 4 ? TA : TB));
     float* my_up = s_up + wid * (3 * UP_SLOT);
     const bool hp_lane = lane >= ET / 4 && lane < ET / 4 + 4;
-    const int up_lane = 4 * min(lane, ET / 4 - 1), hp_off = 4 * (lane - ET / 4);
+    const bool sv_lane = SEL && lane >= UPS_SEL / 4 && lane < (UPS_SEL + PAIR_SEL_ROW) / 4;  // PAIR_SELECT: the track's S[t] behind its hand row
+    const int up_lane = 4 * min(lane, ET / 4 - 1), hp_off = 4 * (lane - ET / 4), sv_off = 4 * (lane - UPS_SEL / 4);
     // (one copy per kernel: as a function in pair_lane.hpp it changed this kernel's schedule)
     auto dma_up = [&](int row, int slot) {
         const size_t r = (size_t)b * T + min(row, T - 1);
-        const float* src = hp_lane ? hand_prev + r * 16 + hp_off : UP + r * ET + up_lane;
+        const float* src = hp_lane ? hand_prev + r * 16 + hp_off : sv_lane ? sel_prev + r * PAIR_SEL_ROW + sv_off : UP + r * ET + up_lane;
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                          (__attribute__((address_space(3))) void*)(my_up + slot * UP_SLOT), 16, 0, 0);
     };
@@ -255,32 +340,28 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
         typedef _Float16 ph2 __attribute__((ext_vector_type(2)));
         bool finite_bound;
         int e1 = 0;
-        f32x2 cs2 = {0.0f, 0.0f};
-        const f32x2 c14 = {16384.0f, 16384.0f};
-        f32x2 upv[GRID ? 1 : 16];   // !GRID: this lane's UP values, scaled
         u32x4 uph[GRID ? 4 : 1], upl[GRID ? 4 : 1];  // GRID: this lane's UP pieces, 8 per k step
-        if constexpr (!GRID) {
-            // the track's scale: every h1 of this track and tile is at most max |UP[t]| + max |UC|
-            // Non-finite embeddings: the clamp of the packed fma below turns a NaN into 0 and saturates an infinity at 1, so they would
-            // come out as finite residuals; the row maxima keep them (absmax_keep_nan), and a track whose bound is not finite gets NaN
-            // for the whole tile - more NaNs than the reference's element-wise propagation, never a finite number in their place.
-            const float bound = hp[13] + mc;
-            finite_bound = bound < INFINITY;  // false for NaN and +inf
-            e1 = range_exponent_bits(__float_as_uint(bound));
-            // h1 = relu(UP + UC) is formed as clamp01(UC cs + UP cs) with cs = 2^(e1 - 14): every sum is at most 1 after the scaling
-            // (exact, a power of two), so the clamp of one packed fma is the ReLU of two values; the conversion multiplies by 2^14.
-            const float cs = __builtin_ldexpf(1.0f, e1 - 14);
-            cs2 = f32x2{cs, cs};
-            // this lane's UP values, scaled: 8 per k step (the same address in the 16 lanes of a k block: LDS broadcast).  (Scaling the row
-            // ONCE in place in LDS - 2 packed multiplies per track instead of 16, as pair_f16w.hip does - measured slower here: 4.06 - 4.13 ->
-            // 4.18 - 4.21 ms at 512 frame-pairs: the write-read round trip through LDS sits on this kernel's critical path.)
+        float upw[SEL ? 32 : 1];  // PAIR_SELECT: this lane's words of -UP[t], 4 per MFMA instruction
+        if constexpr (SEL) {
+            // a track whose bound is not finite gets NaN for the whole tile, as in the other forms
+            finite_bound = sel_finite && hp[13] < INFINITY;
+            // the track's -UP row cut by the wave into its word row: lane L cuts columns 2 L, 2 L + 1; every lane then reads the four
+            // words of its k block per instruction back (LDS broadcast within a k block)
+            uint32_t* my_p = s_upp + wid * 128;
+            {
+                typedef __attribute__((address_space(3))) f32x2 lf32x2;
+                typedef uint32_t pu2 __attribute__((ext_vector_type(2)));
+                const f32x2 v = *reinterpret_cast<const lf32x2*>(up + 2 * lane);
+                *reinterpret_cast<pu2*>(my_p + 2 * lane) =
+                    pu2{cut_select_word(__builtin_ldexpf(-v[0], e_sel)), cut_select_word(__builtin_ldexpf(-v[1], e_sel))};
+            }
 #pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const f32x4 a = *reinterpret_cast<const lf32x4*>(up + 32 * s + 8 * kb), c = *reinterpret_cast<const lf32x4*>(up + 32 * s + 8 * kb + 4);
-                upv[4 * s] = f32x2{a[0], a[1]} * cs2;
-                upv[4 * s + 1] = f32x2{a[2], a[3]} * cs2;
-                upv[4 * s + 2] = f32x2{c[0], c[1]} * cs2;
-                upv[4 * s + 3] = f32x2{c[2], c[3]} * cs2;
+            for (int c = 0; c < 8; ++c) {
+                const f32x4 w4 = __builtin_bit_cast(f32x4, *reinterpret_cast<const u32x4*>(my_p + 16 * c + 4 * kb));
+                upw[4 * c] = w4[0];
+                upw[4 * c + 1] = w4[1];
+                upw[4 * c + 2] = w4[2];
+                upw[4 * c + 3] = w4[3];
             }
         } else {
             finite_bound = grid_finite;
@@ -318,17 +399,7 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
                 }
                 return;
             }
-            // A ds_read_b128 serves lanes {0-3, 12-15, 20-23, 24-27}, {4-11, 16-19, 28-31} (and the same + 32) together - not 16
-            // consecutive lanes (tools/probes/lds_pattern_probe.hip).  In this layout lane = (p, kb) a group mixes rows p of k blocks
-            // kb and kb + 1; with the four k blocks of a step 8 floats apart those fell on each other's banks (every read took 8
-            // cycles instead of 4, the kernel's LDS busy 57 % of the time).  The tile therefore keeps a row k-block-major with the
-            // blocks of a pair 64 floats = one bank round apart: 16 rows x 2 blocks then cover the 64 banks exactly once.
-            const float* ucr = s_uc + (16 * sub + p) * US + ((kb & 1) << 6) + ((kb >> 1) << 5);
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                u[2 * s] = *reinterpret_cast<const f32x4*>(ucr + 8 * s);
-                u[2 * s + 1] = *reinterpret_cast<const f32x4*>(ucr + 8 * s + 4);
-            }
+            // (PAIR_SELECT reads its tile in load_w below)
         };
         auto cut = [&](const f32x4 (&u)[8], u32x4 (&xh)[4], u32x4 (&xl)[4]) {
             if constexpr (GRID) {
@@ -347,24 +418,6 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
                     xl[s] = __builtin_bit_cast(u32x4, l2);
                 }
                 return;
-            }
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-#pragma unroll
-                for (int j2 = 0; j2 < 2; ++j2) {  // the float4 u[2 s + j2] = four values
-                    const f32x4 uu = u[2 * s + j2];
-                    // scaled to [0, 2^14]: high piece = the packed conversion (round to nearest even), residual exact, low piece =
-                    // its conversion.  Only full-register writes: the v_fma_mixlo / mixhi_f16 pair this replaces cost 17.8 cycles per
-                    // two values against 13.4 for multiply + convert (tools/probes/valu_cost_probe.hip) and needed a hand-placed wait
-                    // state between a half-register write and its reader that the compiler does not insert around inline asm.
-                    const f32x2 sa = fma2_relu01(f32x2{uu[0], uu[1]}, cs2, upv[4 * s + 2 * j2]) * c14;
-                    const f32x2 sb = fma2_relu01(f32x2{uu[2], uu[3]}, cs2, upv[4 * s + 2 * j2 + 1]) * c14;
-                    const uint32_t hA = cvt_f16x2(sa[0], sa[1]), hB = cvt_f16x2(sb[0], sb[1]);
-                    xh[s][2 * j2] = hA;
-                    xh[s][2 * j2 + 1] = hB;
-                    xl[s][2 * j2] = cvt_f16x2(f16_res_lo(sa[0], hA), f16_res_hi(sa[1], hA));
-                    xl[s][2 * j2 + 1] = cvt_f16x2(f16_res_lo(sb[0], hB), f16_res_hi(sb[1], hB));
-                }
             }
         };
         auto mma = [&](const u32x4 (&xh)[4], const u32x4 (&xl)[4], f32x4& a_fs, f32x4& a_rc, f32x4& a_fd) {
@@ -391,7 +444,75 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
             *reinterpret_cast<f32x4*>(row + 16) = a_fs;
             if (kb < 2) *reinterpret_cast<f32x4*>(row + 32) = a_fd;
         };
-        {
+        // PAIR_SELECT, per sub-step: the lane's 32 UC words (8 instructions x 4 real k), 32 v_max_f32 against the track's words IN
+        // PLACE - the word of the larger of UC[d][k] and -UP[t][k], cut_select_word's ordering contract -, 16 MFMAs.  The maxima are
+        // inline asm: from fmaxf the compiler cannot know that no word is a signalling NaN and canonicalises both operands first
+        // (three instructions per maximum).  Each statement ends with the two wait states a VALU result needs before an MFMA reads it
+        // (pieces.hpp, hazard rule).
+        auto load_w = [&](int sub, float (&x)[32]) {
+            const uint32_t* ucr = s_ucw + (16 * sub + p) * US + ((kb & 1) << 6) + ((kb >> 1) << 5);
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                const f32x4 w4 = __builtin_bit_cast(f32x4, *reinterpret_cast<const u32x4*>(ucr + 4 * c));
+                x[4 * c] = w4[0];
+                x[4 * c + 1] = w4[1];
+                x[4 * c + 2] = w4[2];
+                x[4 * c + 3] = w4[3];
+            }
+        };
+        auto pick = [&](float (&x)[32]) {
+#pragma unroll
+            for (int q = 0; q < 32; q += 8)
+                asm("v_max_f32 %0, %0, %8\n\tv_max_f32 %1, %1, %9\n\tv_max_f32 %2, %2, %10\n\tv_max_f32 %3, %3, %11\n\t"
+                    "v_max_f32 %4, %4, %12\n\tv_max_f32 %5, %5, %13\n\tv_max_f32 %6, %6, %14\n\tv_max_f32 %7, %7, %15\n\ts_nop 1"
+                    : "+v"(x[q]), "+v"(x[q + 1]), "+v"(x[q + 2]), "+v"(x[q + 3]), "+v"(x[q + 4]), "+v"(x[q + 5]), "+v"(x[q + 6]), "+v"(x[q + 7])
+                    : "v"(upw[SEL ? q : 0]), "v"(upw[SEL ? q + 1 : 0]), "v"(upw[SEL ? q + 2 : 0]), "v"(upw[SEL ? q + 3 : 0]),
+                      "v"(upw[SEL ? q + 4 : 0]), "v"(upw[SEL ? q + 5 : 0]), "v"(upw[SEL ? q + 6 : 0]), "v"(upw[SEL ? q + 7 : 0]));
+        };
+        // per accumulator small to large: the [Wl|Wl] instructions, then the [Wh|Wh] ones (fs: c = 0, 1; rc: 2 .. 5; fd: 6, 7)
+        auto mma_sel = [&](const float (&x)[32], f32x4& a_fs, f32x4& a_rc, f32x4& a_fd) {
+            u32x4 xv[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) xv[c] = __builtin_bit_cast(u32x4, f32x4{x[4 * c], x[4 * c + 1], x[4 * c + 2], x[4 * c + 3]});
+            a_fs = a_rc = a_fd = zero4;
+            a_fs = mfma_16x16x32_f16(sl[0], xv[0], a_fs);
+            a_rc = mfma_16x16x32_f16(sl[2], xv[2], a_rc);
+            a_fd = mfma_16x16x32_f16(sl[6], xv[6], a_fd);
+            a_fs = mfma_16x16x32_f16(sl[1], xv[1], a_fs);
+            a_rc = mfma_16x16x32_f16(sl[3], xv[3], a_rc);
+            a_fd = mfma_16x16x32_f16(sl[7], xv[7], a_fd);
+            a_rc = mfma_16x16x32_f16(sl[4], xv[4], a_rc);
+            a_fs = mfma_16x16x32_f16(sh[0], xv[0], a_fs);
+            a_rc = mfma_16x16x32_f16(sl[5], xv[5], a_rc);
+            a_fd = mfma_16x16x32_f16(sh[6], xv[6], a_fd);
+            a_rc = mfma_16x16x32_f16(sh[2], xv[2], a_rc);
+            a_fs = mfma_16x16x32_f16(sh[1], xv[1], a_fs);
+            a_rc = mfma_16x16x32_f16(sh[3], xv[3], a_rc);
+            a_fd = mfma_16x16x32_f16(sh[7], xv[7], a_fd);
+            a_rc = mfma_16x16x32_f16(sh[4], xv[4], a_rc);
+            a_rc = mfma_16x16x32_f16(sh[5], xv[5], a_rc);
+        };
+        if constexpr (SEL) {
+            // one buffer per sub-step in flight: the words of sub-step s + 2 are read into the buffer whose MFMAs have been issued
+            float xa[32], xb[32];
+            f32x4 fsA, rcA, fdA, fsB, rcB, fdB;
+            load_w(0, xa);
+            load_w(1, xb);
+            pick(xa);
+            mma_sel(xa, fsA, rcA, fdA);
+            load_w(2, xa);
+            store(0, fsA, rcA, fdA);
+            pick(xb);
+            mma_sel(xb, fsB, rcB, fdB);
+            load_w(3, xb);
+            store(1, fsB, rcB, fdB);
+            pick(xa);
+            mma_sel(xa, fsA, rcA, fdA);
+            store(2, fsA, rcA, fdA);
+            pick(xb);
+            mma_sel(xb, fsB, rcB, fdB);
+            store(3, fsB, rcB, fdB);
+        } else {
             f32x4 ua[8], ub[8];
             u32x4 xha[4], xla[4], xhb[4], xlb[4];
             f32x4 fsA, rcA, fdA, fsB, rcB, fdB;
@@ -416,6 +537,7 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
         const lfloat *arow, *abias;
         a4l.per_track(arow, abias);
         // exact descaling: one exponent per track (default form) or one per MLP and workgroup (GRID)
+        if constexpr (SEL) e1 = e_sel;
         const float i_rc = __builtin_ldexpf(1.0f, -((GRID ? ge[1] : e1) + ew_rc)), i_fs = __builtin_ldexpf(1.0f, -((GRID ? ge[0] : e1) + ew_fs)),
                     i_fd = __builtin_ldexpf(1.0f, -((GRID ? ge[2] : e1) + ew_fd));
         f32x4 a_rc2[4], a_fs2[4], a_fd2[2];
@@ -425,14 +547,21 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
             const float* b_rc = s_a4 + A4<F, L_RC2>::OFF + A4<F, L_RC2>::BIAS;
             const float* b_fs = s_a4 + A4<F, L_FS2>::OFF + A4<F, L_FS2>::BIAS;
             const float* b_fd = s_a4 + A4<F, L_FD2>::OFF + A4<F, L_FD2>::BIAS;
+            // PAIR_SELECT: the addend is the track's S[t] = bias + W2 UP[t] (the "+ u" of relu(u + v) = max(v, -u) + u through the linear
+            // layer; row_prep's select role), fetched with the track's row, in the tile's order [rc 16 | fs 16 | fd 8]
+            const lfloat* sv = up + UPS_SEL;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                a_rc2[g] = a4_descale_relu(*reinterpret_cast<const f32x4*>(mine + 4 * g), i_rc, *reinterpret_cast<const f32x4*>(b_rc + 4 * g));
-                a_fs2[g] = a4_descale_relu(*reinterpret_cast<const f32x4*>(mine + 16 + 4 * g), i_fs, *reinterpret_cast<const f32x4*>(b_fs + 4 * g));
+                const f32x4 c_rc = SEL ? *reinterpret_cast<const lf32x4*>(sv + 4 * g) : *reinterpret_cast<const f32x4*>(b_rc + 4 * g);
+                const f32x4 c_fs = SEL ? *reinterpret_cast<const lf32x4*>(sv + 16 + 4 * g) : *reinterpret_cast<const f32x4*>(b_fs + 4 * g);
+                a_rc2[g] = a4_descale_relu(*reinterpret_cast<const f32x4*>(mine + 4 * g), i_rc, c_rc);
+                a_fs2[g] = a4_descale_relu(*reinterpret_cast<const f32x4*>(mine + 16 + 4 * g), i_fs, c_fs);
             }
 #pragma unroll
-            for (int g = 0; g < 2; ++g)
-                a_fd2[g] = a4_descale_relu(*reinterpret_cast<const f32x4*>(mine + 32 + 4 * g), i_fd, *reinterpret_cast<const f32x4*>(b_fd + 4 * g));
+            for (int g = 0; g < 2; ++g) {
+                const f32x4 c_fd = SEL ? *reinterpret_cast<const lf32x4*>(sv + 32 + 4 * g) : *reinterpret_cast<const f32x4*>(b_fd + 4 * g);
+                a_fd2[g] = a4_descale_relu(*reinterpret_cast<const f32x4*>(mine + 32 + 4 * g), i_fd, c_fd);
+            }
         }
         // All forty ReLUs of the layer-2 outputs are done before the first MFMA of layers 3-4 (the empty asm pins them there): a VALU
         // result read by the MFMA right behind it costs two wait states, and the compiler had put one v_max + s_nop 1 in front of
@@ -476,8 +605,8 @@ __global__ __launch_bounds__(64 * WPB) void pair_f16_kernel(const float* __restr
 }
 
 int launch_pair_f16(const float* packed, const float* p16, const float* UP, const float* UC, const float* hand_prev,
-                    const float* hand_det, const float* denom, float* residual, int B, int T, int D, int ld, int nf, bool grid,
-                    hipStream_t st) {
+                    const float* hand_det, const float* sel_prev, const float* denom, float* residual, int B, int T, int D, int ld,
+                    int nf, PairF16Mode mode, hipStream_t st) {
     constexpr int wpb = 8;
     // tracks per workgroup: the T tracks dealt evenly to the ny workgroups of a detection tile, ny the smallest power of two that leaves
     // 512 workgroups (two rounds of the CU array).  A workgroup's prologue - the detection tile and the operand table into LDS behind a
@@ -487,7 +616,9 @@ int launch_pair_f16(const float* packed, const float* p16, const float* UP, cons
     // that has the SIMD to itself (6 870 cycles per track) while waves 4 .. 7 advanced 0.625 tracks per track of theirs, then finished
     // alone - the slow way, one wave per SIMD - for the last quarter of the workgroup's time, with the CU's LDS held.  Dealing the
     // tracks 78 : 48 instead of 63 : 63 lets both finish together (within 7 us of 234): pair stage 4.41 -> 4.16 ms at 512 frame-pairs;
-    // 55 : 100 and 68 : 100 measured 1 - 2 % behind 61.5 : 100.  (s_setprio by phase - the wave in its lane-per-pair phase first, or
+    // 55 : 100 and 68 : 100 measured 1 - 2 % behind 61.5 : 100.  PAIR_SELECT halved the vector instructions, the late wave finds more
+    // free issue slots: 1000 : 760 now (pair stage 7.47 - 7.82 ms against 8.06 - 8.12 at 1000 : 615 and 7.71 - 8.03 at 1000 : 900, one
+    // box, two rounds; profiles/pair_select_ab.txt).  (s_setprio by phase - the wave in its lane-per-pair phase first, or
     // last - with even or uneven tracks: at best equal, 7.71 against 7.65 ms at 1024 frame-pairs; not kept.)
     int ny = 1;
     while ((long)B * cdiv(D, 64) * ny < 512 && cdiv(T, wpb * ny * 2) >= 2) ny *= 2;
@@ -495,20 +626,22 @@ int launch_pair_f16(const float* packed, const float* p16, const float* UP, cons
     int ta = twg / wpb, tb = ta;
     if (wpb == 8) {
         const int per_simd = twg / 4;
-        ta = (per_simd * 1000 + (1000 + 615) / 2) / (1000 + 615);  // to nearest; 615 tracks of a late wave per 1000 of an early one
+        ta = (per_simd * 1000 + (1000 + 760) / 2) / (1000 + 760);  // to nearest; 760 tracks of a late wave per 1000 of an early one
         tb = per_simd - ta;
     }
-    const size_t lds = grid ? PairF16Lds<wpb, true>::bytes : PairF16Lds<wpb, false>::bytes;
     dim3 grd(cdiv(D, 64), cdiv(T, twg), B);
-    if (grid) {
-        (void)hipFuncSetAttribute((const void*)pair_f16_kernel<wpb, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((pair_f16_kernel<wpb, true>), grd, dim3(64 * wpb), lds, st, packed, reinterpret_cast<const uint32_t*>(p16), UP, UC,
-                           hand_prev, hand_det, denom, residual, T, D, ld, nf, twg, ta, tb);
-    } else {
-        (void)hipFuncSetAttribute((const void*)pair_f16_kernel<wpb, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((pair_f16_kernel<wpb, false>), grd, dim3(64 * wpb), lds, st, packed, reinterpret_cast<const uint32_t*>(p16), UP, UC,
-                           hand_prev, hand_det, denom, residual, T, D, ld, nf, twg, ta, tb);
+#define SHASTA_LAUNCH_PAIR_F16(MODE)                                                                                                     \
+    do {                                                                                                                                  \
+        constexpr size_t lds = PairF16Lds<wpb, MODE>::bytes;                                                                              \
+        (void)hipFuncSetAttribute((const void*)pair_f16_kernel<wpb, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);         \
+        hipLaunchKernelGGL((pair_f16_kernel<wpb, MODE>), grd, dim3(64 * wpb), lds, st, packed, reinterpret_cast<const uint32_t*>(p16), UP, \
+                           UC, hand_prev, hand_det, sel_prev, denom, residual, T, D, ld, nf, twg, ta, tb);                                \
+    } while (0)
+    switch (mode) {
+        case PAIR_SELECT: SHASTA_LAUNCH_PAIR_F16(PAIR_SELECT); break;
+        case PAIR_GRID: SHASTA_LAUNCH_PAIR_F16(PAIR_GRID); break;
     }
+#undef SHASTA_LAUNCH_PAIR_F16
     return check_launch("pair_f16");
 }
 

@@ -93,6 +93,23 @@ SH_HD constexpr size_t ap16_scale_offset(int layer, int D) {
 }
 SH_HD constexpr size_t ap16_total(int D) { return ap16_scale_offset(6, D); }
 
+// p16 section of the packed buffer (pair_f16.hip, F = 256), in dwords, and what follows it.  The p16w section behind it holds
+// pair_f16w.hip's fragments at F = 320 and is free at F = 256, where it holds the select form's operands instead:
+//   [0, P16_FRAG_DW)            the second layers as fp16 piece fragments [piece 2][fragment 4][lane 64][4]   (PAIR_GRID)
+//   [P16_FRAG_DW, + 4)          3 int exponents (fs, rc, fd), padded to 4; the p16 section ends here
+//   [P16_SEL_DW, + 2 * 8 KB)    the same weights for select words [piece 2][instruction 8][lane 64][4]: every weight twice, under
+//                               the hi and the lo half of its activation word                               (PAIR_SELECT)
+//   [P16_SUM_DW, + 1792)        float wsum = (high + low piece) of the scaled weights as [k][j]: res_coeff.2 [64][16] | fuse_shape.2
+//                               [32][16] | fuse_det.2 [32][8]: what row_select_kernel multiplies a track's words by
+constexpr int P16_FRAG_DW = 2 * 4 * 64 * 4;
+constexpr int P16_DW = P16_FRAG_DW + 4;
+constexpr int P16W_DW = 2 * 16 * 64 * 4 + 4;
+constexpr int P16_SEL_DW = P16_DW;
+constexpr int P16_SUM_DW = P16_SEL_DW + 2 * 8 * 64 * 4;
+constexpr int PAIR_SEL_SUM = 16 * 64 + 16 * 32 + 8 * 32;
+constexpr int PAIR_SEL_ROW = 40;  // floats per row of PairWs::sel_prev
+static_assert(P16_SUM_DW + PAIR_SEL_SUM <= P16_DW + P16W_DW, "the select operands fit the p16w section");
+
 // n rounded up to a multiple of 4: the padded width Dp of a table of T = N + 2 columns (16-byte aligned rows)
 SH_HD constexpr int pad4(int n) { return (n + 3) / 4 * 4; }
 
@@ -119,8 +136,8 @@ struct PackedLayout {
         bbox_cur = o;   o += (size_t)32;               // [32]       fuse_det.0.bias
         aff0 = o;       o += (size_t)128 * Dp;         // aff.0.weight zero padded to (128, Dp)
         affp = o;       o += ap_layer_offset(6, D) * 256;  // the six aff layers as bf16 piece fragments (aff_pieces.hip)
-        p16 = o;        o += (size_t)(2 * 4 * 64 * 4 + 4);  // second layers of the pair MLPs as fp16 piece fragments + 3 exponents (pair_f16.hip)
-        p16w = o;       o += (size_t)(2 * 16 * 64 * 4 + 4);  // the same as 32x32x16 fragments (pair_f16w.hip: up to 16 fragments x 2 pieces x 1 KB)
+        p16 = o;        o += (size_t)P16_DW;  // second layers of the pair MLPs as fp16 piece fragments + 3 exponents (pair_f16.hip; see P16_*)
+        p16w = o;       o += (size_t)P16W_DW;  // the same as 32x32x16 fragments (pair_f16w.hip: up to 16 fragments x 2 pieces x 1 KB); F = 256: PAIR_SELECT's
         // wemb_prev / wemb_cur as bf16 piece fragments [side][feature block][k step][piece][64 lanes] x 16 B (embed_rows.hip)
         embp = o;       o += (size_t)2 * ((E12 + 31) / 32) * (f / 16) * 3 * 256;
         aff16 = o;      o += ap16_total(D);  // the six aff layers as fp16 piece fragments + their descale factors (aff_f16.hip)

@@ -79,6 +79,34 @@ __device__ __forceinline__ void cut2_f16x8(V v, int e, u32x4& hi, u32x4& lo) {
     }
 }
 
+// ---- select words (pair_f16.hip, PAIR_SELECT; row_prep's per-row vector) -------------------------------------------------------------
+// relu(u + v) = max(v, -u) + u: the pieces of max(v, -u) are the pieces of ONE of two numbers that exist per table row, so they
+// are cut once per row and PICKED per pair.  A value (already range-scaled: |scaled| <= 2^14) becomes one 32-bit word
+//     [ hi : fp16 | lo : fp16 ]     hi = scaled truncated (toward zero) to fp16, lo = fp16(scaled - hi) rounded to nearest,
+// magnitudes below 2^-14 (where hi would be an fp16 denormal) flushed to the word 0.  |hi + lo - scaled| <= 2^-22 |scaled| while
+// lo is a normal fp16, and at most 2^-25 where it is a denormal one.
+// ORDERING CONTRACT: read as fp32 bit patterns the words are monotone in the value,  x <= y  =>  word(x) <= word(y)  as fp32, and
+// equal values give equal words, so v_max_f32 of two words is the word of the larger value.  Why: fp32 orders by sign, then by
+// magnitude bits; the upper half of the word is hi (truncation is monotone, and positive fp16 bit patterns order like their values);
+// among values with equal hi the remainder has the sign of hi (truncation toward zero) and is monotone, rounding is monotone, and
+// the lower half holds it as [sign | magnitude bits] - for a negative hi the set sign bit of lo is a constant of the magnitude
+// comparison (a remainder of exactly 0 gives lo = +0, below every -0 or negative lo in magnitude: still monotone).
+// NEVER A DENORMAL, INF OR NaN as fp32: the fp32 exponent field of a word is the 5 exponent bits of hi and its 3 leading mantissa
+// bits.  hi is a normal fp16 (exponent field >= 1, by the flush), so the fp32 field is >= 8; the range scaling keeps |scaled| <= 2^14
+// (fp16 exponent field <= 29), so the fp32 field is <= 239 < 255.  No mode of v_max_f32 flushes or quiets such an operand.
+// The same function runs in the kernels and in tests/test_pair_select.py's host program.
+__host__ __device__ inline uint32_t cut_select_word(float scaled) {
+    const uint32_t b = __builtin_bit_cast(uint32_t, scaled);
+    if ((b & 0x7fffffffu) < 0x38800000u) return 0u;  // |scaled| < 2^-14 (and -0): +0
+    const float hi = __builtin_bit_cast(float, b & 0xffffe000u);  // 11 significant bits kept: exact in fp16
+    const _Float16 h = (_Float16)hi, l = (_Float16)(scaled - hi);  // the remainder is exact in fp32
+    return (uint32_t)__builtin_bit_cast(uint16_t, h) << 16 | __builtin_bit_cast(uint16_t, l);
+}
+// the value a select word stands for, hi + lo (exact in fp32: the two pieces span at most the 24 bits of the value they were cut from)
+__host__ __device__ inline float select_word_value(uint32_t w) {
+    return (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16)) + (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xffffu));
+}
+
 // HAZARD RULE for the asm helpers below: the compiler inserts the wait states a VALU result needs before an MFMA or a
 // half-register reader consumes it only for its OWN instructions, not around inline asm.  Every result of these helpers must
 // therefore pass through a compiler-generated VALU instruction (e.g. a packed multiply, v_cvt_pk_f16_f32) before it reaches an

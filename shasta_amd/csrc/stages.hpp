@@ -73,9 +73,13 @@ int anchor_stage_fused(const shasta_weights* w, int B, float* feat, float* prev_
 // ---- pair_f16.hip, pair_f16w.hip -----------------------------------------------------------------------------------------------------
 // second layers of the three pair MLPs as fp16 piece fragments: the p16 (F = 256) / p16w (F = 320) section of the packed buffer
 int pair_f16_pack(const shasta_weights* w, float* out, hipStream_t st);
+// how pair_f16_kernel forms the pieces of h1 = relu(UP[t] + UC[d]): PAIR_SELECT picks pre-cut words per pair (the "f16x2" default; needs
+// sel_prev, PairWs), PAIR_GRID adds pre-cut pieces on a fixed grid ("f16grid").  (Cutting every pair's fp32 sum is the form pair_f16w.hip
+// has at F = 320.)
+enum PairF16Mode { PAIR_GRID, PAIR_SELECT };
 int launch_pair_f16(const float* packed, const float* p16, const float* UP, const float* UC, const float* hand_prev,
-                    const float* hand_det, const float* denom, float* residual, int B, int T, int D, int ld, int nf, bool grid,
-                    hipStream_t st);
+                    const float* hand_det, const float* sel_prev, const float* denom, float* residual, int B, int T, int D, int ld,
+                    int nf, PairF16Mode mode, hipStream_t st);
 bool pair_f16w_serves(int F);
 int pair_f16w_pack(const shasta_weights* w, float* out, hipStream_t st);
 // SHASTA_E_UNSUPPORTED when the device does not grant the kernel's LDS
@@ -162,7 +166,7 @@ struct AnchorBoxesWs {
 
 // pair_residual: T = N + 2 table rows per frame
 struct PairWs {
-    size_t up, uc, hand_prev, hand_det, denom, total;
+    size_t up, uc, hand_prev, hand_det, sel_prev, denom, total;
     PairWs(int B, int N, int F) {
         const size_t rows = (size_t)B * (N + 2);
         size_t o = 0;
@@ -170,6 +174,8 @@ struct PairWs {
         uc = ws_take(o, rows * PairDims(F).ET * sizeof(float));  // ... and of the detections
         hand_prev = ws_take(o, rows * 16 * sizeof(float));       // hand tables
         hand_det = ws_take(o, rows * 16 * sizeof(float));
+        // per track row: S[t] = bias2 + W2 UP[t] of the three second layers, [rc 16 | fs 16 | fd 8] (row_prep's select role, F = 256)
+        sel_prev = ws_take(o, rows * PAIR_SEL_ROW * sizeof(float));
         denom = ws_take(o, rows * sizeof(float));                // column norms
         total = o;
     }

@@ -5,6 +5,8 @@ float64 evaluation of the reference formulation on the same tables (oracle = che
  f32      : the factorised evaluation in fp32 (what pair_mfma4_kernel computes, up to summation order)
  cut      : h1 in fp32, cut per pair into two round-to-nearest fp16 pieces under a per-(track, 64-detection tile) power-of-two scale
             (pair_f16.hip, round 2)
+ select   : relu(u + v) = max(v, -u) + u: UC[d] and -UP[t] cut ONCE per row into one orderable word [truncated fp16 high piece | fp16 low
+            piece]; per pair one fp32 maximum picks the word of the larger value, the "+ u" goes through the second layer once per row
  grid     : UP[t] and UC[d] cut ONCE per row into two fp16 pieces on a common fixed grid (high piece = multiple of G, low piece =
             multiple of G 2^-11, G from the largest |UP| of the track group + the largest |UC| of the tile); the per-pair work is then
             packed fp16 adds / maxima only, all exact
@@ -75,9 +77,11 @@ def rows(dt):
     return UP, UC
 
 
-def tails(z_fs, z_rc, z_fd, dt):
-    """layers 3-4 + hand residual + combine from the layer-2 pre-activations (without bias), (T, D, .)"""
+def tails(z_fs, z_rc, z_fd, dt, biased=False):
+    """layers 3-4 + hand residual + combine from the layer-2 pre-activations (without bias unless biased), (T, D, .)"""
     W = {k: v.to(dt) for k, v in w.items()}
+    if biased:
+        W = dict(W, **{k: torch.zeros_like(W[k]) for k in ("fuse_shape.2.bias", "res_coeff.2.bias", "fuse_det.2.bias")})
     h = torch.relu(z_fs + W["fuse_shape.2.bias"])
     h = torch.relu(h @ W["fuse_shape.4.weight"].t() + W["fuse_shape.4.bias"])
     shape = (h @ W["fuse_shape.6.weight"].t() + W["fuse_shape.6.bias"])[..., 0]
@@ -123,6 +127,7 @@ def report(name, res):
     err = (res.double() - ref).abs()
     print("%-28s max %.3e  rms %.3e   (relative to max|residual| = %.3g: %.2e / %.2e)" % (
         name, float(err.max()), float(err.pow(2).mean().sqrt()), scale, float(err.max()) / scale, float(err.pow(2).mean().sqrt()) / scale))
+    return float(err.max()), float(err.pow(2).mean().sqrt())
 
 
 # f32 factorised
@@ -130,7 +135,7 @@ UP32, UC32 = rows(torch.float32)
 h1 = torch.relu(UP32[:, None, :] + UC32[None, :, :])
 W32 = w
 z = [h1[..., SL[n]] @ W32[n].t() for n in ("fuse_shape.2.weight", "res_coeff.2.weight", "fuse_det.2.weight")]
-report("f32 factorised", tails(z[0], z[1], z[2], torch.float32))
+F32_ERR = report("f32 factorised", tails(z[0], z[1], z[2], torch.float32))
 
 # cut per pair (round 2): scale per (track, 64-detection tile)
 UPd, UCd = UP32.double(), UC32.double()
@@ -178,6 +183,86 @@ for hb, lb in ((a.hbits, a.lbits), (10, 10), (11, 10)):
             xh[t0:t1, d0:d1], xl[t0:t1, d0:d1] = h2, l2
     z = layer2(xh, xl)
     report("grid %d+%d bits, %d tracks" % (hb, lb, a.group), tails(z[0], z[1], z[2], torch.float32))
+
+
+# ---- select: relu(u + v) = max(v, -u) + u.  UC[d] and -UP[t] are cut ONCE per row into a 32-bit word [hi fp16 | lo fp16] (hi = the
+# scaled value truncated to fp16, lo = fp16(remainder), same sign; scaled magnitudes below 2^-14 flushed to +0), which read as fp32 is
+# monotone in the value: per pair and hidden unit the work is one fp32 maximum of two words.  The "+ u" goes through the linear
+# second layer as a per-row vector S[t] = W2 UP[t], formed once per row from the pieces of -UP[t] with the same piece products (all
+# four: a word feeds both of its pieces to every weight fragment, [Wh|Wh] and [Wl|Wl]).
+def trunc16(x):
+    """float64 x (already scaled, |x| < 2^16) -> its truncation to 11 significant bits; magnitudes below 2^-14 flushed to +0"""
+    m, e = torch.frexp(x)
+    h = torch.ldexp(torch.trunc(m * 2048.0), e - 11)
+    return torch.where(x.abs() < 2.0 ** -14, torch.zeros_like(x), h)
+
+
+def cut_select(x, hb=11):
+    """the two pieces of a select word: hb = 11 is the word of pieces.hpp; hb = 12 models 'one bit more' (a 12-bit high piece with the
+    low piece rounded to nearest on it), which no fp16 word holds - a bound on what a wider word could gain"""
+    if hb == 11:
+        h = trunc16(x)
+    else:
+        m, e = torch.frexp(x)
+        h = torch.where(x.abs() < 2.0 ** -14, torch.zeros_like(x), torch.ldexp(torch.trunc(m * 2.0 ** hb), e - hb))
+    l = torch.where(h == 0, torch.zeros_like(x), (x - h).to(torch.float16).double())
+    return h, l
+
+
+def f32r(x):
+    return x.float().double()
+
+
+def select_run(group, hb=11, chunk=16):
+    """-> z per MLP (T, D, out) fp32 WITH the layer-2 bias: what the descale fma leaves.  The fp32 accumulator of the f16 MFMA is
+    modelled as one rounding per instruction: 16 real k (hi and lo interleaved along the instruction's 32 k) per instruction, the
+    [Wl|Wl] fragments first, then [Wh|Wh] (small to large)."""
+    names = ("fuse_shape.2.weight", "res_coeff.2.weight", "fuse_det.2.weight")
+    out = {n: torch.empty(T, D, W2[n][0].shape[0], dtype=torch.float64) for n in names}
+    # S[t]: pieces of -UP[t] under the row's own scale (row_prep does not know the tile), float64 accumulation, stored as fp32
+    S = {}
+    mrow = UPd.abs().amax(1).clamp_min(1e-300)
+    srow = torch.pow(2.0, 13 - torch.floor(torch.log2(mrow)))[:, None]
+    rh, rl = cut_select(-UPd * srow, hb)
+    rh, rl = rh / srow, rl / srow
+    for n in names:
+        wh, wl = W2[n]
+        k = SL[n]
+        S[n] = f32r(w[n.replace("weight", "bias")].double()[None] - (rh[:, k] + rl[:, k]) @ (wh + wl).t())
+    for d0 in range(0, D, 64):
+        d1 = min(D, d0 + 64)
+        mc = float(UCd[d0:d1].abs().max())
+        for t0 in range(0, T, group):
+            t1 = min(T, t0 + group)
+            m = float(UPd[t0:t1].abs().max()) + mc
+            s = 2.0 ** (13 - np.floor(np.log2(m))) if m > 0 else 1.0
+            ch, cl = cut_select(UCd[d0:d1] * s, hb)
+            ph, pl = cut_select(-UPd[t0:t1] * s, hb)
+            pick = (UCd[d0:d1][None] >= -UPd[t0:t1][:, None])            # = the comparison of the words (monotone, ties equal)
+            xh_ = torch.where(pick, ch[None], ph[:, None]) / s
+            xl_ = torch.where(pick, cl[None], pl[:, None]) / s
+            for n in names:
+                wh, wl = W2[n]
+                k = SL[n]
+                acc = torch.zeros(t1 - t0, d1 - d0, wh.shape[0], dtype=torch.float64)
+                for c0 in range(k.start, k.stop, chunk):
+                    c = slice(c0, c0 + chunk)
+                    wc = slice(c0 - k.start, c0 - k.start + chunk)
+                    acc = f32r(acc + (xh_[..., c] + xl_[..., c]) @ wl[:, wc].t())
+                for c0 in range(k.start, k.stop, chunk):
+                    c = slice(c0, c0 + chunk)
+                    wc = slice(c0 - k.start, c0 - k.start + chunk)
+                    acc = f32r(acc + (xh_[..., c] @ wh[:, wc].t() + xl_[..., c] @ wh[:, wc].t()))
+                out[n][t0:t1, d0:d1] = f32r(acc + S[n][t0:t1, None, :])     # the descale fma: one rounding
+    return [out[n].float() for n in names]
+
+
+# the gate: the bar of tests/test_hip_parity.py::test_pair_kernels_are_fp32_accurate with `select` in place of `f16x2`
+for grp, hb in ((a.group, 11), (T, 11), (a.group, 12), (T, 12)):
+    zs = select_run(grp, hb)
+    mx, rms = report("select %d-bit high, %d tracks" % (hb, grp), tails(zs[0], zs[1], zs[2], torch.float32, biased=True))
+    ok = mx <= 2.0 * F32_ERR[0] + 1e-7 * scale and rms <= 1.5 * F32_ERR[1] + 1e-8 * scale and mx <= 1e-5 * scale
+    print("    gate (max <= 2 x f32 + 1e-7 scale, rms <= 1.5 x f32 + 1e-8 scale, max <= 1e-5 scale): %s" % ("PASS" if ok else "FAIL"))
 
 # per-MLP grids: the three k ranges (fuse_shape | res_coeff | fuse_det) get their own G (their accumulators are separate)
 print("row maxima per k range: UP", [float(UPd[:, SL[n]].abs().max()) for n in SL], "UC", [float(UCd[:, SL[n]].abs().max()) for n in SL])
