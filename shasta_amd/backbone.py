@@ -40,14 +40,13 @@ Registration: the class is NOT put into BACKBONES at import (a string config `ty
 user decides).  Either pass the class itself, `backbone=dict(type=shasta_amd.backbone.SpMiddleResNetFHD, num_input_features=5,
 ds_factor=8)`, or call `shasta_amd.backbone.register()` once and keep the reference's string configs.
 """
-import ctypes
 import math
 
 import numpy as np
 import torch
 from torch import nn
 
-from . import hip, sync_bn
+from . import frozen, hip, sync_bn
 from .neck import build_norm_layer
 from .registry import BACKBONES
 
@@ -176,7 +175,7 @@ class _Level:
         return self._subm
 
 
-class SpMiddleResNetFHD(nn.Module):
+class SpMiddleResNetFHD(frozen.FrozenStage):
     def __init__(self, num_input_features=128, norm_cfg=None, name="SpMiddleResNetFHD", batch_statistics=False, **kwargs):
         super().__init__()
         self.name = name
@@ -202,25 +201,10 @@ class SpMiddleResNetFHD(nn.Module):
                                    block(128, "res3"), block(128, "res3"))
         self.extra_conv = nn.Sequential(SparseConv3d(128, 128, (3, 1, 1), (2, 1, 1), bias=False), bn(128), nn.ReLU())
 
-        # HIP-side state (not parameters, not in state_dict)
-        self._packed = None      # id(conv) -> byte tensor: the eval pack (BatchNorm folded with the running statistics)
-        self._packed_raw = None  # id(conv) -> byte tensor: the raw pack (conv + bias) of a layer that runs on batch statistics
-        self._packed_key = None
-        self._batch = None       # during a train()-mode forward: id(conv) -> its BatchNorm1d in training mode, and the scratch
-
-    # ---- state_dict -----------------------------------------------------------------------------------------
-    def _apply(self, fn, *a, **k):  # .to() / .cuda() / .float(): parameter storage moves -> drop the packed layers
-        self.invalidate_weights_cache()
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):  # (spconv 1.x weight layouts are adapted per convolution: _SparseConv._load_from_state_dict)
-        self.invalidate_weights_cache()
-        return super().load_state_dict(*a, **k)
-
-    def invalidate_weights_cache(self):
-        """Forget the packed layers; the next forward re-packs them.  They follow in-place writes and load_state_dict by themselves
-        (pointer + version checks); call this after a write that bumps no version counter."""
-        self._packed_key = None
+        # HIP-side state (not parameters, not in state_dict); the packed layers are in `_cache` (frozen.py): slot i is the eval pack of
+        # pair i (BatchNorm folded with the running statistics), slot (i, "raw") its raw pack (conv + bias) for batch statistics
+        self._stats = frozen.BatchStatistics(self._cache, "shasta_bn_rows_finalize_f32")
+        self._run = None  # this forward's layers: see `_ensure_packed`
 
     # ---- packed layers --------------------------------------------------------------------------------------
     def _pairs(self):
@@ -250,58 +234,52 @@ class SpMiddleResNetFHD(nn.Module):
             raise hip.ShastaHipError("SpMiddleResNetFHD: fp32 voxel features only, got %s" % voxel_features.dtype)
         params = []
         for conv, bn in self._pairs():
-            if not (isinstance(bn, (nn.BatchNorm1d, sync_bn.SyncBatchNorm)) and bn.affine and bn.track_running_stats):
+            if not frozen.servable_norm(bn, (nn.BatchNorm1d, sync_bn.SyncBatchNorm)):
                 raise hip.ShastaHipError("SpMiddleResNetFHD: only BatchNorm1d (or its sync_bn.SyncBatchNorm conversion) with affine parameters "
                                          "and running statistics is served, got %s" % type(bn).__name__)
-            if self.training and bn.training and bn.momentum is None:
-                raise hip.ShastaHipError("SpMiddleResNetFHD: BatchNorm1d(momentum=None) (cumulative averaging of the running statistics) "
-                                         "is not served in train() mode")
+            if self.training and bn.training:
+                frozen.refuse_cumulative_average("SpMiddleResNetFHD", "BatchNorm1d", bn)
             params += self._tensors(conv, bn)
-        if any(t.dtype != torch.float32 for t in params):
+        if not frozen.all_fp32(params):
             raise hip.ShastaHipError("SpMiddleResNetFHD: fp32 parameters only")
-        if torch.is_grad_enabled() and (voxel_features.requires_grad or any(t.requires_grad for t in params)):
+        if frozen.wants_autograd(voxel_features, params):
             raise hip.ShastaHipError("SpMiddleResNetFHD: autograd is not served (no backward): run under torch.no_grad() or freeze the "
                                      "parameters with requires_grad_(False)")
 
-    def _batch_layers(self):
-        """id(conv) -> BatchNorm1d of the layers that run on batch statistics in this forward: torch's rule per BatchNorm module."""
-        if not (self.training and self.batch_statistics):
-            return {}
-        return {id(conv): bn for conv, bn in self._pairs() if bn.training}
+    def _ensure_packed(self, dev):
+        """id(conv) -> (eval slot, packed layer, bn): every layer packed for its tensors as they are.  torch's rule per BatchNorm module:
+        a layer whose `bn` is in training mode runs on batch statistics in this forward - the raw pack, and `bn` - else the eval pack, None."""
+        train, run = self.training and self.batch_statistics, {}
+        for i, (conv, bn) in enumerate(self._pairs()):
+            raw = train and bn.training
+            pk = self._cache.get((i, "raw") if raw else i, self._tensors(conv, bn), dev, lambda: self._pack(conv, bn, dev, raw),
+                                 reads_statistics=not raw)
+            run[id(conv)] = (i, pk, bn if raw else None)
+        return run
 
-    def _ensure_packed(self, dev, batch=()):
-        """Eval packs of the layers on running statistics, raw packs of those in `batch`; both kept under one pointer + version key."""
-        pairs = self._pairs()
-        key = tuple((t.data_ptr(), t._version) for conv, bn in pairs for t in self._tensors(conv, bn)) + (str(dev),)
-        if self._packed is None or self._packed_key != key:
-            self._packed, self._packed_raw, self._packed_key = {}, {}, key
+    def _pack(self, conv, bn, dev, raw):
         lib = hip.load()
-        for conv, bn in pairs:
-            raw = id(conv) in batch
-            packed = self._packed_raw if raw else self._packed
-            if id(conv) in packed:
-                continue
-            k, s, p = conv.geometry
-            cin, cout, K = conv.in_channels, conv.out_channels, int(np.prod(k))
-            nbytes = lib.shasta_spconv_layer_packed_bytes(cin, cout, K) if lib.shasta_spconv_supported(cin, cout, *k, *s, *p) else 0
-            if nbytes == 0:
-                raise hip.ShastaHipError("SpMiddleResNetFHD: a %d -> %d convolution with kernel %s, stride %s, padding %s is not served by "
-                                         "shasta_spconv_layer_f32" % (cin, cout, k, s, p))
-            if any(t.device != dev for t in self._tensors(conv, bn)):
-                raise hip.ShastaHipError("SpMiddleResNetFHD: parameters and input are on different devices")
-            w, g, b, mean, var = [t.detach().contiguous() for t in self._tensors(conv, bn)[:5]]
-            bias = None if conv.bias is None else conv.bias.detach().contiguous()
-            buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            if raw:
-                if not lib.shasta_bn_rows_supported(cout):
-                    raise hip.ShastaHipError("SpMiddleResNetFHD: batch statistics over rows of %d channels are not served" % cout)
-                hip.check(lib.shasta_spconv_layer_pack_raw_f32(hip.ptr(w), hip.ptr(bias), cin, cout, K, hip.ptr(buf), nbytes, hip.stream_ptr()),
-                          "shasta_spconv_layer_pack_raw_f32")
-            else:
-                hip.check(lib.shasta_spconv_layer_pack_f32(hip.ptr(w), hip.ptr(bias), hip.ptr(g), hip.ptr(b), hip.ptr(mean), hip.ptr(var),
-                                                           float(bn.eps), cin, cout, K, hip.ptr(buf), nbytes, hip.stream_ptr()),
-                          "shasta_spconv_layer_pack_f32")
-            packed[id(conv)] = buf
+        k, s, p = conv.geometry
+        cin, cout, K = conv.in_channels, conv.out_channels, int(np.prod(k))
+        nbytes = lib.shasta_spconv_layer_packed_bytes(cin, cout, K) if lib.shasta_spconv_supported(cin, cout, *k, *s, *p) else 0
+        if nbytes == 0:
+            raise hip.ShastaHipError("SpMiddleResNetFHD: a %d -> %d convolution with kernel %s, stride %s, padding %s is not served by "
+                                     "shasta_spconv_layer_f32" % (cin, cout, k, s, p))
+        if any(t.device != dev for t in self._tensors(conv, bn)):
+            raise hip.ShastaHipError("SpMiddleResNetFHD: parameters and input are on different devices")
+        w, g, b, mean, var = [t.detach().contiguous() for t in self._tensors(conv, bn)[:5]]
+        bias = None if conv.bias is None else conv.bias.detach().contiguous()
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        if raw:
+            if not lib.shasta_bn_rows_supported(cout):
+                raise hip.ShastaHipError("SpMiddleResNetFHD: batch statistics over rows of %d channels are not served" % cout)
+            hip.check(lib.shasta_spconv_layer_pack_raw_f32(hip.ptr(w), hip.ptr(bias), cin, cout, K, hip.ptr(buf), nbytes, hip.stream_ptr()),
+                      "shasta_spconv_layer_pack_raw_f32")
+        else:
+            hip.check(lib.shasta_spconv_layer_pack_f32(hip.ptr(w), hip.ptr(bias), hip.ptr(g), hip.ptr(b), hip.ptr(mean), hip.ptr(var),
+                                                       float(bn.eps), cin, cout, K, hip.ptr(buf), nbytes, hip.stream_ptr()),
+                      "shasta_spconv_layer_pack_f32")
+        return buf
 
     # ---- forward --------------------------------------------------------------------------------------------
     @staticmethod
@@ -312,51 +290,30 @@ class SpMiddleResNetFHD(nn.Module):
         return torch.empty(nbytes, dtype=torch.uint8, device=dev)
 
     def _layer(self, x, n_in, nbr, conv, residual=None, relu=True):
-        n_out, K = nbr.shape
-        if self._batch is not None and id(conv) in self._batch["bn"]:
-            return self._layer_batch(x, n_in, nbr, conv, residual, relu)
-        pk = self._packed[id(conv)]
-        out = torch.empty(n_out, conv.out_channels, dtype=torch.float32, device=nbr.device)
-        hip.check(hip.load().shasta_spconv_layer_f32(hip.ptr(x), n_in, conv.in_channels, hip.ptr(nbr), n_out, K, hip.ptr(pk), pk.numel(),
-                                                     conv.out_channels, hip.ptr(residual), 1 if relu else 0, hip.ptr(out), hip.stream_ptr()),
-                  "shasta_spconv_layer_f32")
-        return out
-
-    def _check_rows(self, conv, n_out):
-        """torch.nn.functional.batch_norm's check for a layer on batch statistics, before any launch of that layer."""
-        if self._batch is not None and id(conv) in self._batch["bn"] and id(conv) not in self._batch["synced"] and n_out < 2:
-            raise ValueError("Expected more than 1 value per channel when training, got input size %s"
-                             % (torch.Size([n_out, conv.out_channels]),))
-
-    def _layer_batch(self, x, n_in, nbr, conv, residual, relu):
-        """A layer whose BatchNorm1d is in training mode: raw convolution into a scratch, batch statistics of its rows, finalize (updates
-        the module's running statistics in place), apply in place with the residual and the ReLU."""
-        lib = hip.load()
-        bn, st = self._batch["bn"][id(conv)], self._batch
+        """One layer into a new (n_out, C) tensor.  Where its BatchNorm1d is in training mode: the raw convolution, the batch statistics of
+        its rows, finalize (updates the module's running statistics in place), apply in place with the residual and the ReLU."""
+        lib, s = hip.load(), hip.stream_ptr()
         n_out, K = nbr.shape
         C = conv.out_channels
+        slot, pk, bn = self._run[id(conv)]
         self._check_rows(conv, n_out)
-        s = hip.stream_ptr()
-        pk = self._packed_raw[id(conv)]
         y = torch.empty(n_out, C, dtype=torch.float32, device=nbr.device)
-        hip.check(lib.shasta_spconv_layer_f32(hip.ptr(x), n_in, conv.in_channels, hip.ptr(nbr), n_out, K, hip.ptr(pk), pk.numel(), C, None, 0,
-                                              hip.ptr(y), s), "shasta_spconv_layer_f32")
-        mm, stat, ws = st["mean_m2"], st["stat"], st["workspace"]
-        world = st["synced"].get(id(conv), 1)
-        if world > 1:  # statistics of all ranks: the stats kernel writes the front of the local record, gather, merged finalize
-            ranks = st["ranks"]
-            hip.check(lib.shasta_bn_rows_stats_f32(hip.ptr(y), n_out, C, hip.ptr(ranks.local(C, world)), hip.ptr(ws), ws.numel(), s),
-                      "shasta_bn_rows_stats_f32")
-            ranks.finalize(bn, C, n_out, stat, s)
-        else:
-            hip.check(lib.shasta_bn_rows_stats_f32(hip.ptr(y), n_out, C, hip.ptr(mm), hip.ptr(ws), ws.numel(), s), "shasta_bn_rows_stats_f32")
-            hip.check(lib.shasta_bn_rows_finalize_f32(hip.ptr(mm), C, float(n_out), float(bn.eps), float(bn.momentum), hip.ptr(stat),
-                                                      hip.ptr(bn.running_mean), hip.ptr(bn.running_var),
-                                                      ctypes.c_void_p(bn.num_batches_tracked.data_ptr()), s), "shasta_bn_rows_finalize_f32")
-        st["updated"].append(conv)
+        args = (hip.ptr(x), n_in, conv.in_channels, hip.ptr(nbr), n_out, K, hip.ptr(pk), pk.numel(), C)
+        if bn is None:
+            hip.check(lib.shasta_spconv_layer_f32(*args, hip.ptr(residual), 1 if relu else 0, hip.ptr(y), s), "shasta_spconv_layer_f32")
+            return y
+        hip.check(lib.shasta_spconv_layer_f32(*args, None, 0, hip.ptr(y), s), "shasta_spconv_layer_f32")
+        stat = self._stats.layer(slot, bn, C, n_out, lambda mm, ws: hip.check(lib.shasta_bn_rows_stats_f32(
+            hip.ptr(y), n_out, C, hip.ptr(mm), hip.ptr(ws), ws.numel(), s), "shasta_bn_rows_stats_f32"), s)
         hip.check(lib.shasta_bn_rows_apply_f32(hip.ptr(y), n_out, C, hip.ptr(stat), hip.ptr(bn.weight.detach()), hip.ptr(bn.bias.detach()),
                                                hip.ptr(residual), 1 if relu else 0, hip.ptr(y), s), "shasta_bn_rows_apply_f32")
         return y
+
+    def _check_rows(self, conv, n_out):
+        """torch.nn.functional.batch_norm's check for a layer on batch statistics, before any launch of that layer."""
+        bn = self._run[id(conv)][2]
+        if bn is not None:
+            frozen.refuse_single_value(bn, (n_out, conv.out_channels))
 
     def _blocks(self, x, lvl, mods):
         for m in mods:
@@ -402,29 +359,16 @@ class SpMiddleResNetFHD(nn.Module):
         dev = voxel_features.device
         B = int(batch_size)
         grid = tuple(int(v) for v in (np.array(input_shape[::-1]) + [1, 0, 0]))  # sparse_shape, scn.py:181
-        batch = self._batch_layers()
-        self._ensure_packed(dev, batch)
+        self._run = self._ensure_packed(dev)
         x = voxel_features.contiguous()
         coords = coors.int().contiguous()
-        if not batch:
-            return self._forward(x, coords, B, grid)
-        width = max(bn.num_features for bn in batch.values())
-        # id(conv) -> world of the layers whose SyncBatchNorm shares its statistics with other ranks
-        synced = {k: sync_bn.synced_world(bn) for k, bn in batch.items() if sync_bn.synced_world(bn) > 1}
-        if synced and x.shape[0] == 0:  # (before the first collective; a non-empty cloud has at least 1 row at every level)
-            raise ValueError("SpMiddleResNetFHD: an empty local input cannot take part in synchronised batch statistics")
-        ranks = sync_bn.RankStats(max(batch[k].num_features for k in synced), max(synced.values()), dev) if synced else None
-        self._batch = dict(bn=batch, synced=synced, ranks=ranks, updated=[], mean_m2=torch.empty(2 * width, dtype=torch.float32, device=dev),
-                           stat=torch.empty(2 * width, dtype=torch.float32, device=dev),
-                           workspace=torch.empty(lib.shasta_bn_rows_workspace_bytes(width), dtype=torch.uint8, device=dev))
-        try:
-            return self._forward(x, coords, B, grid)
-        finally:
-            # the kernels wrote the running statistics through raw pointers (no version bump): an eval pack folded from the old ones,
-            # left by an earlier forward under the same key, is stale now
-            for conv in self._batch["updated"]:
-                self._packed.pop(id(conv), None)
-            self._batch = None
+        batch = [bn for _, _, bn in self._run.values() if bn is not None]  # the layers on batch statistics in this forward
+        if batch:
+            # (before the first collective; a non-empty cloud has at least 1 row at every level)
+            if x.shape[0] == 0 and any(sync_bn.synced_world(bn) > 1 for bn in batch):
+                raise ValueError("SpMiddleResNetFHD: an empty local input cannot take part in synchronised batch statistics")
+            self._stats.reserve(batch, lib.shasta_bn_rows_workspace_bytes(max(bn.num_features for bn in batch)), dev)
+        return self._forward(x, coords, B, grid)
 
     def _forward(self, x, coords, B, grid):
         lib = hip.load()

@@ -38,7 +38,7 @@ from collections import OrderedDict
 import torch
 from torch import nn
 
-from . import hip
+from . import frozen, hip
 from .registry import HEADS
 
 NUSC_COMMON_HEADS = OrderedDict([("reg", (2, 2)), ("height", (1, 2)), ("dim", (3, 2)), ("rot", (2, 2)), ("vel", (2, 2))])
@@ -80,7 +80,7 @@ def _get(cfg, key, default=None):
 
 
 @HEADS.register_module
-class CenterHead(nn.Module):
+class CenterHead(frozen.FrozenStage):
     def __init__(self, in_channels=[512], tasks=[], dataset="nuscenes", weight=0.25, code_weights=[], common_heads=dict(), logger=None,
                  init_bias=-2.19, share_conv_channel=64, num_hm_conv=2, dcn_head=False):
         super().__init__()
@@ -105,9 +105,8 @@ class CenterHead(nn.Module):
         if logger is not None:
             logger.info("Finish CenterHead Initialization")
 
-        # HIP-side state (not parameters, not in state_dict)
-        self._packed = None      # (shared layer, [per task (first-convs layer, final convs, widths array, names, channel counts)])
-        self._packed_key = None
+        # HIP-side state (not parameters, not in state_dict); `_cache` (frozen.py) holds the packed layers, slots "shared" and the task index
+        self._packed = None      # (shared layer, [per task (first-convs layer, final convs, widths array, names, channel counts)]) of this forward
         self._bufs = None        # the shared map and the tasks' 64 x heads map
 
     # ---- the nn form --------------------------------------------------------------------------------------------
@@ -116,23 +115,10 @@ class CenterHead(nn.Module):
         return [task(x) for task in self.tasks]
 
     # ---- kernel path --------------------------------------------------------------------------------------------
-    def _apply(self, fn, *a, **k):
-        self.invalidate_weights_cache()
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        self.invalidate_weights_cache()
-        return super().load_state_dict(*a, **k)
-
-    def invalidate_weights_cache(self):
-        """Forget the packed layers; the next kernel-path forward re-packs them.  They follow in-place writes, optimizer steps and
-        load_state_dict by themselves (pointer + version checks); call this after a write that bumps no version counter."""
-        self._packed_key = None
-
     def _layout(self):
         """None when a layer is outside what the kernels serve; else per task [(name, first conv, bn, last conv)]."""
         def bn_ok(bn):
-            return isinstance(bn, nn.BatchNorm2d) and bn.affine and bn.track_running_stats
+            return frozen.servable_norm(bn, nn.BatchNorm2d)
 
         sc = self.shared_conv
         if not (isinstance(sc[0], nn.Conv2d) and bn_ok(sc[1])):
@@ -156,22 +142,14 @@ class CenterHead(nn.Module):
     def _bn_tensors(conv, bn):
         return [conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var]
 
-    def _params(self, lay):
-        ts = self._bn_tensors(self.shared_conv[0], self.shared_conv[1])
-        for heads in lay:
-            for _, c0, bn, c3 in heads:
-                ts += self._bn_tensors(c0, bn) + [c3.weight, c3.bias]
-        return ts
+    def _task_tensors(self, heads):
+        return [t for _, c0, bn, c3 in heads for t in self._bn_tensors(c0, bn) + [c3.weight, c3.bias]]
 
     def _kernel_path(self, x, lay):
         if self.training or lay is None or x.dim() != 4 or x.dtype != torch.float32 or not x.is_cuda:
             return False
-        params = self._params(lay)
-        if any(t.dtype != torch.float32 for t in params):
-            return False
-        if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in params)):
-            return False
-        return True
+        params = self._bn_tensors(self.shared_conv[0], self.shared_conv[1]) + [t for heads in lay for t in self._task_tensors(heads)]
+        return frozen.all_fp32(params) and not frozen.wants_autograd(x, params)
 
     @staticmethod
     def _pack_bn_layer(lib, convs, bns, dev):
@@ -205,17 +183,17 @@ class CenterHead(nn.Module):
         return out
 
     def _ensure_packed(self, lay, dev):
-        key = tuple((t.data_ptr(), t._version) for t in self._params(lay)) + (str(dev),)
-        if self._packed is not None and self._packed_key == key:
-            return self._packed
+        """The shared layer and one entry per task, each packed for its own tensors as they are."""
         lib = hip.load()
-        shared = self._pack_bn_layer(lib, [self.shared_conv[0]], [self.shared_conv[1]], dev)
-        tasks = []
-        for heads in lay:
+        sc = self.shared_conv
+
+        def task(heads):
             first = self._pack_bn_layer(lib, [h[1] for h in heads], [h[2] for h in heads], dev)
             widths = (ctypes.c_int * len(heads))(*[h[3].out_channels for h in heads])
-            tasks.append((first, self._pack_final([h[3] for h in heads], dev), widths, [h[0] for h in heads], [h[3].out_channels for h in heads]))
-        self._packed, self._packed_key = (shared, tasks), key
+            return first, self._pack_final([h[3] for h in heads], dev), widths, [h[0] for h in heads], [h[3].out_channels for h in heads]
+
+        shared = self._cache.get("shared", self._bn_tensors(sc[0], sc[1]), dev, lambda: self._pack_bn_layer(lib, [sc[0]], [sc[1]], dev))
+        self._packed = (shared, [self._cache.get(t, self._task_tensors(heads), dev, lambda: task(heads)) for t, heads in enumerate(lay)])
         return self._packed
 
     def forward_raw(self, x):

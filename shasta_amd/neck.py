@@ -35,13 +35,11 @@ refusal does not apply (every rank has B >= 1).  The set of layers on batch stat
 frozen set-up guarantees it); a rank that raises before a collective leaves the others to torch.distributed's timeout, as with any
 collective.  The collective is not capturable in a graph.  World 1, or no initialised process group: the calls and bits of BatchNorm2d.
 """
-import ctypes
-
 import numpy as np
 import torch
 from torch import nn
 
-from . import hip, sync_bn
+from . import frozen, hip, sync_bn
 from .registry import NECKS
 
 C3S1, C3S2, C1, D2 = 0, 1, 2, 3  # include/shasta_hip.h SHASTA_NECK_*
@@ -71,7 +69,7 @@ def build_norm_layer(cfg, num_features):
 
 
 @NECKS.register_module
-class RPN(nn.Module):
+class RPN(frozen.FrozenStage):
     def __init__(self, layer_nums, ds_layer_strides, ds_num_filters, us_layer_strides, us_num_filters, num_input_features,
                  norm_cfg=None, name="rpn", logger=None, batch_statistics=False, **kwargs):
         super().__init__()
@@ -112,13 +110,10 @@ class RPN(nn.Module):
         if logger is not None:
             logger.info("Finish RPN Initialization")
 
-        # HIP-side state (not parameters, not in state_dict)
-        self._packed = None      # one byte tensor per layer
-        self._packed_key = None  # one (pointer, version) key per layer
-        self._stale = set()      # layers whose running statistics the kernels wrote: weights packed, alpha / beta' out of date
+        # HIP-side state (not parameters, not in state_dict); `_cache` (frozen.py) holds the packed layers, slot = index in the plan
+        self._packed = None      # this forward's packed layers: one byte tensor per layer, in plan order
         self._bufs = None        # the two ping-pong buffers
-        self._train_bufs = None  # train() mode: mean_m2, stat, the statistics workspace
-        self._rank_stats = None  # train() mode with a SyncBatchNorm over several ranks: the record and gather buffers (sync_bn.RankStats)
+        self._train_bufs = frozen.BatchStatistics(self._cache, "shasta_bn_maps_finalize_f32")  # train() mode: mean_m2, stat, workspace
         self._plan_now = None    # the chain of kernel layers and the module identities it was built from: see `_plan`
         self._plan_ids = None
 
@@ -163,8 +158,8 @@ class RPN(nn.Module):
         ids = tuple(id(m) for seq in (*self.blocks, *self.deblocks) for m in seq)
         if ids != self._plan_ids:
             self._plan_now, self._plan_ids = self._make_plan(), ids
-            self._packed = self._packed_key = None
-            self._stale = set()
+            self._packed = None
+            self._cache.clear()
         return self._plan_now
 
     def _make_plan(self):
@@ -175,7 +170,7 @@ class RPN(nn.Module):
         plan = []
 
         def bn_ok(bn):
-            return isinstance(bn, (nn.BatchNorm2d, sync_bn.SyncBatchNorm)) and bn.affine and bn.track_running_stats
+            return frozen.servable_norm(bn, (nn.BatchNorm2d, sync_bn.SyncBatchNorm))
 
         for i, block in enumerate(self.blocks):
             mods = list(block)
@@ -201,48 +196,29 @@ class RPN(nn.Module):
                     return None
         return plan
 
-    def _apply(self, fn, *a, **k):  # .to() / .cuda() / .float(): parameter storage moves -> drop the packed layers
-        self.invalidate_weights_cache()
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        self.invalidate_weights_cache()
-        return super().load_state_dict(*a, **k)
-
-    def invalidate_weights_cache(self):
-        """Forget the packed layers; the next kernel-path forward re-packs them.  They follow in-place writes, optimizer steps and
-        load_state_dict by themselves (pointer + version checks); call this after a write that bumps no version counter."""
-        self._packed_key = None
-        self._stale = set()
-
     @staticmethod
     def _tensors(conv, bn):
         return [conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var]
 
     def _ensure_packed(self, dev, batch=()):
-        """Every layer packed for its tensors as they are (pointer + version key per layer).  A layer in `batch` (it runs on batch
-        statistics in this forward) reads the weight section only, so alpha / beta' marked stale by an earlier train() forward do not
-        make it re-pack; every other layer is re-packed when stale."""
-        if self._packed is None or self._packed_key is None:
-            self._packed, self._packed_key, self._stale = [None] * len(self._plan_now), [None] * len(self._plan_now), set()
+        """Every layer packed for its tensors as they are.  A layer in `batch` (it runs on batch statistics in this forward) reads the
+        weight section only, so alpha / beta' marked stale by an earlier train() forward do not make it re-pack."""
+        self._packed = [self._cache.get(i, self._tensors(conv, bn), dev, lambda: self._pack(kind, conv, bn, dev), reads_statistics=i not in batch)
+                        for i, (kind, conv, bn, _) in enumerate(self._plan_now)]
+
+    def _pack(self, kind, conv, bn, dev):
         lib = hip.load()
-        packed = self._packed
-        for i, (kind, conv, bn, _) in enumerate(self._plan_now):
-            key = tuple((t.data_ptr(), t._version) for t in self._tensors(conv, bn)) + (str(dev),)
-            if packed[i] is not None and self._packed_key[i] == key and (i in batch or i not in self._stale):
-                continue
-            ts = [t.detach().contiguous() for t in self._tensors(conv, bn)]
-            cin, cout = conv.in_channels, conv.out_channels
-            if kind == C1:  # the reference's 1x1 deblock is a Conv2d, (Cout, Cin, 1, 1); the C1 kind takes ConvTranspose2d's (Cin, Cout, 1, 1)
-                ts[0] = ts[0].reshape(cout, cin).t().contiguous()
-            nbytes = lib.shasta_neck_layer_packed_bytes(kind, cin, cout)
-            if nbytes == 0:
-                raise hip.ShastaHipError("RPN: layer %d -> %d channels is not served by shasta_neck_layer_f32" % (cin, cout))
-            buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            hip.check(lib.shasta_neck_layer_pack_f32(*[hip.ptr(t) for t in ts], float(bn.eps), kind, cin, cout, hip.ptr(buf), nbytes,
-                                                     hip.stream_ptr()), "shasta_neck_layer_pack_f32")
-            packed[i], self._packed_key[i] = buf, key
-            self._stale.discard(i)
+        ts = [t.detach().contiguous() for t in self._tensors(conv, bn)]
+        cin, cout = conv.in_channels, conv.out_channels
+        if kind == C1:  # the reference's 1x1 deblock is a Conv2d, (Cout, Cin, 1, 1); the C1 kind takes ConvTranspose2d's (Cin, Cout, 1, 1)
+            ts[0] = ts[0].reshape(cout, cin).t().contiguous()
+        nbytes = lib.shasta_neck_layer_packed_bytes(kind, cin, cout)
+        if nbytes == 0:
+            raise hip.ShastaHipError("RPN: layer %d -> %d channels is not served by shasta_neck_layer_f32" % (cin, cout))
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        hip.check(lib.shasta_neck_layer_pack_f32(*[hip.ptr(t) for t in ts], float(bn.eps), kind, cin, cout, hip.ptr(buf), nbytes,
+                                                 hip.stream_ptr()), "shasta_neck_layer_pack_f32")
+        return buf
 
     def _shapes(self, H, W):
         """Per layer of the plan: (H, W) of its input and of its output; None when a layer is not served at this map size."""
@@ -273,44 +249,18 @@ class RPN(nn.Module):
         for i, ((_, conv, bn, _), s) in enumerate(zip(self._plan_now, shapes)):
             if not bn.training:
                 continue
-            if bn.momentum is None:
-                raise hip.ShastaHipError("RPN: BatchNorm2d(momentum=None) (cumulative averaging of the running statistics) is not served "
-                                         "in train() mode")
-            if B * s[2] * s[3] < 2 and sync_bn.synced_world(bn) == 1:  # (several ranks: B >= 1 each, at least 2 values in total)
-                raise ValueError("Expected more than 1 value per channel when training, got input size %s"
-                                 % (torch.Size([B, conv.out_channels, s[2], s[3]]),))
+            frozen.refuse_cumulative_average("RPN", "BatchNorm2d", bn)
+            frozen.refuse_single_value(bn, (B, conv.out_channels, s[2], s[3]))
             if not lib.shasta_bn_maps_supported(conv.out_channels):
                 raise hip.ShastaHipError("RPN: batch statistics over maps of %d channels are not served" % conv.out_channels)
             batch.append(i)
         return frozenset(batch)
 
-    def _ensure_train_bufs(self, B, shapes, batch, dev):
-        lib = hip.load()
-        cmax = max(self._plan_now[i][1].out_channels for i in batch)
-        need = max(lib.shasta_bn_maps_workspace_bytes(B, self._plan_now[i][1].out_channels, shapes[i][2] * shapes[i][3]) for i in batch)
-        tb = self._train_bufs
-        if tb is None or tb[0].device != dev or tb[0].numel() < 2 * cmax or tb[2].numel() < need:
-            self._train_bufs = None
-            tb = self._train_bufs = (torch.empty(2 * cmax, dtype=torch.float32, device=dev), torch.empty(2 * cmax, dtype=torch.float32, device=dev),
-                                     torch.empty(need, dtype=torch.uint8, device=dev))
-        return tb
-
-    def _ensure_rank_stats(self, width, world, dev):
-        rs = self._rank_stats
-        if rs is None or rs.width < width or rs.world < world or rs.device != dev:
-            self._rank_stats = None
-            rs = self._rank_stats = sync_bn.RankStats(width, world, dev)
-        return rs
-
     def _kernel_path(self, x):
         if (self.training and not self.batch_statistics) or self._plan is None or x.dim() != 4 or x.dtype != torch.float32:
             return False
         params = [t for _, conv, bn, _ in self._plan_now for t in self._tensors(conv, bn)]
-        if any(t.dtype != torch.float32 for t in params):
-            return False
-        if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in params)):
-            return False
-        return True
+        return frozen.all_fp32(params) and not frozen.wants_autograd(x, params)
 
     def forward(self, x):
         if not self._kernel_path(x):
@@ -338,10 +288,8 @@ class RPN(nn.Module):
         out = torch.empty(B, ctot, oh, ow, dtype=torch.float32, device=dev)
         stream = hip.stream_ptr()
         if batch:
-            mm, stat, ws = self._ensure_train_bufs(B, shapes, batch, dev)
-            worlds = {i: sync_bn.synced_world(self._plan_now[i][2]) for i in batch}  # > 1: statistics shared with other ranks
-            if max(worlds.values()) > 1:
-                ranks = self._ensure_rank_stats(max(self._plan_now[i][1].out_channels for i in batch if worlds[i] > 1), max(worlds.values()), dev)
+            ws_bytes = max(lib.shasta_bn_maps_workspace_bytes(B, self._plan_now[i][1].out_channels, shapes[i][2] * shapes[i][3]) for i in batch)
+            self._train_bufs.reserve([self._plan_now[i][2] for i in batch], ws_bytes, dev)
         cur, nxt = x, 0
         for i, ((kind, conv, bn, role), pk, s) in enumerate(zip(self._plan_now, self._packed, shapes)):
             if role == "block":
@@ -353,18 +301,8 @@ class RPN(nn.Module):
             if i in batch:  # raw convolution into the destination, batch statistics of it, finalize, apply in place
                 C, plane = conv.out_channels, s[2] * s[3]
                 hip.check(lib.shasta_neck_layer_raw_f32(*args), "shasta_neck_layer_raw_f32")
-                world = worlds[i]
-                local = ranks.local(C, world) if world > 1 else mm  # (several ranks: the front of the local record)
-                hip.check(lib.shasta_bn_maps_stats_f32(hip.ptr(dst), B, C, plane, total, off, hip.ptr(local), hip.ptr(ws), ws.numel(), stream),
-                          "shasta_bn_maps_stats_f32")
-                self._stale.add(i)  # (before the launch that writes the running statistics)
-                if world > 1:  # one all-gather of the record, the merged finalize on the device
-                    ranks.finalize(bn, C, B * plane, stat, stream)
-                else:
-                    hip.check(lib.shasta_bn_maps_finalize_f32(hip.ptr(mm), C, float(B * plane), float(bn.eps), float(bn.momentum), hip.ptr(stat),
-                                                              hip.ptr(bn.running_mean), hip.ptr(bn.running_var),
-                                                              ctypes.c_void_p(bn.num_batches_tracked.data_ptr()), stream),
-                              "shasta_bn_maps_finalize_f32")
+                stat = self._train_bufs.layer(i, bn, C, B * plane, lambda mm, ws: hip.check(lib.shasta_bn_maps_stats_f32(
+                    hip.ptr(dst), B, C, plane, total, off, hip.ptr(mm), hip.ptr(ws), ws.numel(), stream), "shasta_bn_maps_stats_f32"), stream)
                 hip.check(lib.shasta_bn_maps_apply_f32(hip.ptr(dst), B, C, plane, total, off, hip.ptr(stat), hip.ptr(bn.weight.detach()),
                                                        hip.ptr(bn.bias.detach()), 1, stream), "shasta_bn_maps_apply_f32")
             else:

@@ -123,7 +123,7 @@ class RankStats:
     written by `fill_` on an int64 view of the record's tail, the merge runs on the device in float64, sequentially in rank order, on the
     same gathered bytes on every rank - `stat` and the running statistics are bit-equal across ranks.
 
-    One object per forward, sized for the widest layer and reused by every layer (a layer of C channels takes the front 8 C + 8 bytes of
+    One object per module (`frozen.BatchStatistics` keeps it), sized for the widest layer and reused by every layer (a layer of C channels takes the front 8 C + 8 bytes of
     the record and the front R (8 C + 8) bytes of the gather buffer).  The reuse is safe under stream ordering: the stats kernel that
     writes the record, the collective and the finalize that reads the gathered records are all ordered on the caller's stream - the
     blocking collective makes the current stream wait for it, and starts only after the work queued on that stream before it - so the
